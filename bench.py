@@ -34,6 +34,13 @@ backward, bucketed gradient all-reduce (overlapped with backward) and fused
 optimizer update.  The JSON line carries the communication breakdown of the timed
 steps: bucket count, all-reduce ms and exposed (not overlapped) communication ms.
 
+A plain run sets up, warms up, times ``--steps`` steps and prints the JSON line.
+``--dump-outputs DIR`` also writes what the last timed step computed (rank 0: loss, logits,
+master weights after the update) as ``DIR/<name>.npy``; seeds are fixed, so two runs with the
+same arguments start from identical inputs and weights.  ``--full`` adds what the headline
+figure does not need, all of it at N > 1: the replica-consistency check after warmup, the
+all-reduce bus-bandwidth and transport probes and the DP-engine A/B cells after the timed steps.
+
 ``--model tiny --device cpu`` runs the same code path on a small bottleneck ResNet on
 CPU ranks over gloo (CPU tests of the launch contract); its numbers are not a metric.
 """
@@ -68,8 +75,16 @@ def parse(argv=None):
     ap.add_argument("--grad-reduce-dtype", choices=("auto", "bf16", "fp32", "native"), default=None,
                     help="wire dtype of the gradient all-reduce (default auto: bf16 for every bucket of a bf16 model)")
     ap.add_argument("--json-out", default=None)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps rank 0 writes what the last timed step computed as DIR/<name>.npy "
+                         "(float32): its loss and logits and the fp32 master weights after its update (a fixed, "
+                         "seeded sample of them beyond 8M elements)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need (N > 1): the replica-consistency check "
+                         "after warmup, the all-reduce bus-bandwidth and transport probes and the DP-engine A/B "
+                         "cells after the timed region")
     ap.add_argument("--ab", type=int, default=1,
-                    help="N > 1: after the timed region, a <= 5-step A/B per DP-engine cell (per-bucket optimizer "
+                    help="--full at N > 1: after the timed region, a <= 5-step A/B per DP-engine cell (per-bucket optimizer "
                          "on/off x buckets 16/32/64 MB x torch/native RCCL; CLOUD_AMD_BENCH_AB selects cells)")
     ap.add_argument("--ab-steps", type=int, default=5)
     ap.add_argument("--via-run", type=int, default=int(os.environ.get("CLOUD_AMD_BENCH_VIA_RUN", "1")),
@@ -95,7 +110,77 @@ def via_run(args):
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     from cloud_amd.utils import benchlaunch
 
-    benchlaunch.launch_via_run(os.path.abspath(__file__), args.gpus, device=args.device)
+    script = os.path.abspath(__file__)
+    here = os.path.dirname(script)
+    scratch = None
+    if not os.access(here, os.W_OK):
+        # A source tree this user cannot write to (a shared or write-protected checkout): run()
+        # can neither create ./jobs there nor add its wrapper to the staged copy, which takes over
+        # the mode of the directory it is staged from.  Stage from a writable directory of links
+        # to this one's entries instead, and keep the job directories beside it.
+        import tempfile
+
+        scratch = tempfile.mkdtemp(prefix="cloud_amd_bench_")
+        mirror = os.path.join(scratch, "src")
+        os.mkdir(mirror)
+        for name in os.listdir(here):
+            os.symlink(os.path.join(here, name), os.path.join(mirror, name))
+        script = os.path.join(mirror, os.path.basename(script))
+        os.environ.setdefault("CLOUD_AMD_JOBS_DIR", os.path.join(scratch, "jobs"))
+    argv = None
+    if args.dump_outputs:
+        # the ranks run from the staged copy of this directory: hand them the caller's DIR
+        argv = benchlaunch.strip_flag(sys.argv[1:], "--dump-outputs")
+        argv += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
+    try:
+        benchlaunch.launch_via_run(script, args.gpus, device=args.device, argv=argv)
+    except SystemExit as e:
+        if scratch and not e.code:  # a failed job keeps its directory: the error names its logs
+            _remove_tree(scratch)
+        raise
+
+
+def _remove_tree(path):
+    """rmtree of a staged copy whose directories may have taken over read-only modes."""
+    import shutil
+
+    for d, _, _ in os.walk(path):
+        try:
+            os.chmod(d, 0o700)
+        except OSError:
+            pass
+    shutil.rmtree(path, ignore_errors=True)
+
+
+DUMP_WEIGHTS_MAX = 8 << 20  # elements: 32 MB of the 64 MB a dump may take; the logits take 4 MB
+
+
+def dump_outputs(path, loss, logits, arenas):
+    """``--dump-outputs``: what the last timed step handed back -- its loss, its logits and the
+    fp32 master weights its update left -- as ``<name>.npy`` (float32) under ``path``.  Beyond
+    ``DUMP_WEIGHTS_MAX`` elements the weights are sampled at fixed positions (seeded, sorted),
+    the same positions in every run of the same model."""
+    import numpy as np
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+
+    def save(name, t):
+        np.save(os.path.join(path, name + ".npy"), t.detach().float().cpu().numpy().astype(np.float32, copy=False))
+
+    save("loss", loss.reshape(1))
+    if logits is not None:
+        save("logits", logits[:max(1, DUMP_WEIGHTS_MAX // max(logits[0].numel(), 1))])  # first rows, <= 32 MB
+    total = sum(a.master.numel() for a in arenas)
+    for k, a in enumerate(arenas):
+        w = a.master.detach().reshape(-1)
+        if total > DUMP_WEIGHTS_MAX:
+            n = max(1, w.numel() * DUMP_WEIGHTS_MAX // total)
+            g = torch.Generator(device="cpu")
+            g.manual_seed(4321 + k)
+            idx = torch.randperm(w.numel(), generator=g)[:n].sort().values
+            w = w[idx.to(w.device)]
+        save("weights_arena%d" % k, w)
 
 
 def main():
@@ -159,6 +244,8 @@ def main():
     def fwd_bwd():
         with trace.range("forward"):
             logits = model(x)
+            if args.dump_outputs:
+                holder["logits"] = logits.detach()  # --dump-outputs writes the last step's
             loss, _ = softmax_cross_entropy(logits, y, denom=B)
         with trace.range("backward"):
             loss.backward()
@@ -193,10 +280,10 @@ def main():
     pacer = opt.pacer
     for _ in range(max(args.warmup - 1, 0)):
         loss = step_fn()
-    # desync check once after warmup (world > 1): every replica must hold identical
+    # --full: desync check once after warmup (world > 1): every replica must hold identical
     # all-reduced gradients (fp64 fingerprint over all arenas, all-gathered)
     replicas_consistent = None
-    if world > 1:
+    if world > 1 and args.full:
         try:
             replicas_consistent = bool(reducer.check_consistency())
         except RuntimeError as e:
@@ -238,9 +325,10 @@ def main():
     per_rank_ms = [v / args.steps * 1000.0 for v in dist_env.all_gather_floats(t1 - t0, device)]
     elapsed = dist_env.all_reduce_max(t1 - t0, device)
     ms = elapsed / args.steps * 1000.0
-    busbw = dist_env.allreduce_busbw(device) if world > 1 else None  # after the timed steps
-    # both transports on the same buffers: decides the default data plane (CLOUD_AMD_COMM)
-    probe = dist_env.comm_probe(device) if world > 1 else None
+    # --full: bus bandwidth after the timed steps, and both transports on the same buffers
+    # (decides the default data plane, CLOUD_AMD_COMM)
+    busbw = dist_env.allreduce_busbw(device) if (world > 1 and args.full) else None
+    probe = dist_env.comm_probe(device) if (world > 1 and args.full) else None
     ips = global_batch * args.steps / elapsed
     first_lat = dist_env.all_reduce_max(first_step_latency, device)
     if run_to_first is not None:
@@ -248,6 +336,8 @@ def main():
     comm["allreduce_ms"] = dist_env.all_reduce_max(comm["allreduce_ms"], device)
     comm["exposed_comm_ms"] = dist_env.all_reduce_max(comm["exposed_comm_ms"], device)
     final_loss = float(loss.detach().float().item()) if loss is not None else float("nan")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, holder.get("logits"), opt.arenas)
     try:
         from cloud_amd import monitoring
 
@@ -316,11 +406,11 @@ def main():
             with open(args.json_out, "w") as f:
                 f.write(line + "\n")
 
-    # N > 1: a bounded step-level A/B of the DP knobs no one-GPU box can settle (per-bucket
-    # optimizer, bucket size, transport) -- cloud_amd/utils/dp_ab.py
+    # --full at N > 1: a bounded step-level A/B of the DP knobs no one-GPU box can settle
+    # (per-bucket optimizer, bucket size, transport) -- cloud_amd/utils/dp_ab.py
     from cloud_amd.utils import dp_ab
 
-    cells = dp_ab.cells_from_env() if (world > 1 and args.ab) else []
+    cells = dp_ab.cells_from_env() if (world > 1 and args.full and args.ab) else []
     if cells:
         dp_ab.teardown(reducer)
         ab = []

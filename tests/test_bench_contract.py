@@ -25,13 +25,15 @@ def _json_lines(out):
 
 
 def test_bench_two_ranks_via_run_cpu(tmp_path):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"] + TINY,
+    # --full: the transport probes and the DP-engine A/B run only there
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full"] + TINY,
                        env=_env(tmp_path), capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     lines = _json_lines(r.stdout)
     assert len(lines) == 1, r.stdout[-3000:]
     j = lines[0]
     assert j["n_gpus"] == 2 and j["config"]["parallelism"] == "dp2"
+    assert j["replicas_consistent"] is True
     assert j["launched_via"] == "cloud_amd.run()"
     assert j["run_to_first_step_s"] is not None and j["run_to_first_step_s"] > 0
     ph = j["startup_phases_rank0"]  # run() -> first step split at the wrapper and the script body
@@ -69,6 +71,33 @@ def test_bench_two_ranks_via_run_cpu(tmp_path):
     assert len(job) == 1
     meta = json.load(open(tmp_path / "jobs" / job[0] / "job.json"))
     assert meta["world_size"] == 2 and meta["state"] == "SUCCEEDED"
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """Without --full a 2-rank run times its steps and nothing else (no consistency check, no
+    transport probes, no A/B cells); --dump-outputs DIR (relative to the caller's directory)
+    receives the last timed step's loss, logits and master weights from rank 0 as float32."""
+    import numpy as np
+
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dump-outputs", "dump"]
+                       + TINY, env=_env(tmp_path), capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    lines = _json_lines(r.stdout)
+    assert len(lines) == 1, r.stdout[-3000:]
+    j = lines[0]
+    assert j["n_gpus"] == 2 and j["steps"] == 2 and j["warmup"] == 1
+    assert j["unit"] == "images/sec" and j["higher_is_better"] is True and j["dtype"] == "fp32"
+    assert j["ms_per_step"] > 0 and abs(j["value"] - 8 * 1000.0 / j["ms_per_step"]) <= 0.01 * j["value"]
+    assert "dp_ab" not in j and j["replicas_consistent"] is None
+    assert j["comm"]["comm_probe"] is None and j["comm"]["busbw_gbs"] is None
+    assert len(j["step_stats_rank0"]["host_launch_ms_steps"]) == 2  # --steps is the number of timed steps
+    files = sorted(os.listdir(tmp_path / "dump"))
+    assert files[:2] == ["logits.npy", "loss.npy"] and any(f.startswith("weights_arena") for f in files)
+    arrays = {f: np.load(tmp_path / "dump" / f) for f in files}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+    assert arrays["logits.npy"].shape == (4, 10) and arrays["loss.npy"].shape == (1,)
+    assert abs(float(arrays["loss.npy"][0]) - j["final_loss"]) < 1e-3
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
 
 
 def test_bench_too_many_gpus_fails(tmp_path):
