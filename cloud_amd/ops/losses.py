@@ -99,15 +99,26 @@ def softmax_cross_entropy(logits, labels, *, denom=None, label_smoothing=0.0, ac
     the MultiWorkerMirrored ``compute_average_loss`` convention.  ``acc`` (fp32 [3] on the
     device): ``acc += [sum of row losses, sum of correct flags, rows] * acc_weight``
     inside the loss kernel (Keras loss / accuracy metric state without per-step syncs).
+
+    Ignored rows: a label outside ``[0, C)`` (-1, C, ...) marks its row as ignored on both
+    engines (HIP kernels and the torch fallback): the row's loss, its ``correct`` flag and its
+    logits gradient are 0.  The row still counts in ``denom`` (and in ``acc[2]``): the mean
+    is over all rows, not over the valid ones.  ``correct`` follows the smallest-index rule
+    on tied maxima.
     """
-    B = logits.shape[0]
+    B, C = logits.shape
     denom = B if denom is None else denom
     labels = labels.long()
     if logits.dtype in (torch.bfloat16, torch.float32) and _ext.use_native(logits, labels):
         return _XentFn.apply(logits, labels, denom, label_smoothing, acc, acc_weight)
     lf = logits.float()
-    per = F.cross_entropy(lf, labels, reduction="none", label_smoothing=label_smoothing)
-    correct = (lf.argmax(-1) == labels).float()
+    valid = (labels >= 0) & (labels < C)
+    safe = torch.where(valid, labels, torch.zeros_like(labels))
+    per = F.cross_entropy(lf, safe, reduction="none", label_smoothing=label_smoothing) * valid.to(lf.dtype)
+    # first index of the row maximum (the kernels' tie rule), not argmax's unspecified one
+    cols = torch.arange(C, device=lf.device).expand_as(lf)
+    first = torch.where(lf == lf.max(-1, keepdim=True).values, cols, cols.new_full((), C)).min(-1).values
+    correct = ((first == labels) & valid).float()
     if acc is not None:
         with torch.no_grad():
             acc += torch.stack([per.sum(), correct.sum(), per.new_tensor(float(B))]).to(acc.device) * float(acc_weight)

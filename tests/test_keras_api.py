@@ -243,3 +243,42 @@ def test_backward_with_seed_matches_autograd_and_skips_sympy():
     out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300,
                          cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     assert out.stdout.strip().splitlines()[-1] == "False", out.stdout + out.stderr
+
+
+def test_softmax_xent_fallback_ignores_out_of_range_labels():
+    """The torch engine of ops.softmax_cross_entropy keeps the HIP kernels' ignored-label
+    contract: a label outside [0, C) gives its row zero loss, zero `correct` and zero
+    gradient, while the row still counts in `denom` and in acc[2]; `correct` takes the
+    smallest index among tied maxima."""
+    import torch
+    import torch.nn.functional as F
+
+    from cloud_amd import ops
+
+    torch.manual_seed(3)
+    B, C = 9, 7
+    z = torch.randn(B, C, dtype=torch.float32)
+    z[1, 2] = z[1, 5] = z[1].max() + 1.0  # tie: index 2 wins
+    z[4, 0] = z[4, 6] = z[4].max() + 1.0  # tie: index 0 wins, label 6 is wrong
+    y = torch.randint(0, C, (B,))
+    y[1], y[4] = 2, 6
+    y[0], y[3], y[6] = -1, C, -1
+    valid = (y >= 0) & (y < C)
+    for ls in (0.0, 0.1):
+        zz = z.clone().requires_grad_()
+        acc = torch.tensor([1.5, 2.0, 3.0])
+        loss, correct = ops.softmax_cross_entropy(zz, y, denom=2 * B, label_smoothing=ls, acc=acc, acc_weight=0.5)
+        (3 * loss).backward()
+        zr = z.double().requires_grad_()
+        per = F.cross_entropy(zr[valid], y[valid], reduction="none", label_smoothing=ls)
+        (3 * per.sum() / (2 * B)).backward()
+        first = torch.tensor([min(c for c in range(C) if z[b, c] == z[b].max()) for b in range(B)])
+        ref_correct = ((first == y) & valid).float()
+        assert ref_correct[1] == 1 and ref_correct[4] == 0
+        torch.testing.assert_close(loss.double(), per.sum().detach() / (2 * B), atol=1e-6, rtol=1e-6)
+        assert torch.equal(correct, ref_correct)
+        assert torch.equal(zz.grad[~valid], torch.zeros_like(zz.grad[~valid]))
+        torch.testing.assert_close(zz.grad.double(), zr.grad, atol=1e-7, rtol=1e-5)
+        ref_acc = torch.tensor([1.5, 2.0, 3.0]).double() + torch.stack(
+            [per.sum().detach(), ref_correct.sum().double(), torch.tensor(float(B)).double()]) * 0.5
+        torch.testing.assert_close(acc.double(), ref_acc, atol=1e-5, rtol=1e-6)
