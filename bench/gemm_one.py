@@ -1,6 +1,6 @@
 """One GEMM shape, repeated: the target of rocprofv3 counter passes on a single kernel.
 
-    CLOUD_AMD_GEMM_CORE=pp256 python bench/gemm_one.py 4096 4096 4096 --layout 0 --iters 50
+    CLOUD_AMD_GEMM_CORE=vp8 python bench/gemm_one.py 4096 4096 4096 --layout 0 --iters 50
 """
 import argparse
 import os

@@ -60,11 +60,8 @@ _VARS = [
     Var("CLOUD_AMD_GEMM", str, "native", "dense GEMMs: 'native' or 'torch'", "ops"),
     Var("CLOUD_AMD_CONV", str, "native", "convolutions: 'native' or 'torch'", "ops"),
     Var("CLOUD_AMD_GEMM_CORE", str, "auto", "GEMM core: 'auto' (128x128 LDS-DMA core plus the 256x256 two-phase "
-        "core of ca_gemm256p8.h for large GEMMs), 'glds_ring' (128 core plus the 256x256 ring core), 'glds' (128 "
-        "core only), 'vp8' / 'v256' (the two-phase / ring 256 core whenever M, N >= 256), 'glds8', 'reg' "
-        "(register staging); 'glds_ring' / 'v256' / 'glds8' need CLOUD_AMD_BUILD_EXPERIMENTAL=1", "ops"),
-    Var("CLOUD_AMD_BUILD_EXPERIMENTAL", bool, False, "build: also compile the experiment-only GEMM cores (glds8, "
-        "256x256 ring, stream-K, 256x128) into _C for A/B runs", "ops"),
+        "core of ca_gemm256p8.h for large GEMMs), 'glds' (128 core only), 'vp8' (the two-phase 256 core whenever "
+        "M, N >= 256), 'reg' (register staging); any other name selects 'auto'", "ops"),
     Var("CLOUD_AMD_WGRAD_BLOCKS", int, 512, "convolution weight gradients: split-K so that about this many "
         "workgroups run (tiles x splits); fewer splits = less fp32 slab traffic, more = fuller CUs", "ops"),
     Var("CLOUD_AMD_WGRAD_BLOCKS_SMALLM", int, 512, "convolution weight gradients with <= 128 output channels "
@@ -75,9 +72,6 @@ _VARS = [
         "(round 4, same box: 640 -> 6,993 / 6,993 seq/s, 768 -> 6,962 / 6,952, 1024 -> 6,892 / 6,911, 512 -> "
         "6,865 / 6,896; profiles/r4_s36/)",
         "ops"),
-    Var("CLOUD_AMD_GEMM_256X128", bool, False, "GEMMs whose 256 x 128 grid fills whole rounds (and 256 x 256 does "
-        "not) on the 256 x 128 single-phase core (csrc/include/ca_gemm256p8.h); measured slower than the 128 core "
-        "on BERT's shapes", "ops"),
     Var("CLOUD_AMD_DENSE_WGRAD_256", bool, False, "dense-layer weight gradients whose 256 x 256 tiles times a split "
         "count fill one round of the chip (BERT QKV / FFN) run on the two-phase 256 core with that split (measured "
         "3 % slower on BERT than the 128 core's 1024-workgroup split: 6,749 / 6,754 vs 6,952 / 6,940 seq/s)", "ops"),
@@ -126,10 +120,6 @@ _VARS = [
         "default: 4-wave blocks walking four rows per wave)", "ops"),
     Var("CLOUD_AMD_GEMM_256X96", bool, True, "forward GEMMs whose 256 x 96 grid fills whole rounds while the 128 x "
         "128 grid leaves a partial one (BERT QKV, M = 8192, N = 2304) run on 256 x 96 tiles; 0 = off (A/B)", "ops"),
-    Var("CLOUD_AMD_GEMM_STREAMK", int, 0, "two-phase 256 x 256 GEMM: 0 off (default; measured slower than the "
-        "128 x 128 core on BERT's M = 8192 shapes), 1 stream-K on under-filled grids, 2 wherever allowed (tests)", "ops"),
-    Var("CLOUD_AMD_LN_BWD8", bool, False, "retired round-5 A/B knob (8-wave LayerNorm backward, measured 1.5 % slower "
-        "and removed); ignored", "ops"),
     Var("CLOUD_AMD_BN_FIN_RPG", int, 512, "BatchNorm statistics finalize: partial rows per group block (64-512)", "ops"),
     Var("CLOUD_AMD_BN_FIN_MERGED", bool, True, "BatchNorm statistics from many partial rows: group reduction and "
         "per-channel finalize in ONE launch (last block per 64 channels finalizes, agent-scope ticket); 0 = two "
@@ -169,9 +159,8 @@ _VARS = [
     Var("CLOUD_AMD_BN_FOLD_WGRAD1", bool, False, "the same one-pass input + weight gradient for stage 1's conv1 with "
         "bn1's backward apply (K = 64 -> N = 256: dz1 never written, four output chunks per tile)", "ops"),
     Var("CLOUD_AMD_XA_N256", int, 3, "transform-A GEMMs (BN folded into a 1x1 conv) with N a multiple of 256: "
-        "1 = 128 x 256 tiles on 16-wave workgroups (each A tile transformed once), 2 = 128 x 256 on 8 waves "
-        "(CLOUD_AMD_BUILD_EXPERIMENTAL builds only), "
-        "3 = 16 waves with two K tiles' operands in flight (coefficients staged in LDS; K <= 2048), "
+        "1 = 128 x 256 tiles on 16-wave workgroups (each A tile transformed once), "
+        "3 (and any other value) = 16 waves with two K tiles' operands in flight (coefficients staged in LDS; K <= 2048), "
         "0 = 128 x 128 tiles.  Only the fold sites CLOUD_AMD_BN_FOLD_MAX_N admits reach them (ResNet-50 stage 3 "
         "at the default; measured in docs/performance.md, round 6)", "ops"),
     Var("CLOUD_AMD_XA_WAVES", int, 8,"128 x 128 transform-A GEMMs (BN folded into the 1x1 convs): 8-wave "

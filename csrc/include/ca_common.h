@@ -22,6 +22,14 @@ inline bool ca_debug_sync() {
   return on;
 }
 
+// On/off switch read from the environment (host side; call sites keep the result in a
+// function-local `static const bool`).  A default-on switch turns off only when the value's
+// first character is '0', a default-off switch turns on only when it is '1'.
+inline bool env_switch(const char* name, bool dflt) {
+  const char* e = getenv(name);
+  return dflt ? !(e && e[0] == '0') : (e && e[0] == '1');
+}
+
 #define CA_WAVE 64
 
 #define CA_HIP_CHECK(expr)                                                     \

@@ -33,7 +33,7 @@
 // Barriers are bare s_barrier (a __syncthreads fence would wait for vmcnt(0) and drain the
 // prefetch); LDS writes are ordered by lgkmcnt(0) before them.
 #pragma once
-#include "ca_gemm256.h"
+#include "ca_mfma_core.h"
 
 namespace ca {
 

@@ -108,7 +108,6 @@ struct CoreParams {
   FastDiv div_wq, div_hq, div_nw;
   int split_xcd;  // split-K grids: deal (split, tile) ranges to XCDs split-major (blk_pos)
   int prw_chunks; // persistent resident-weight core: column chunks of BN (0 / 1 = the whole N resident)
-  unsigned long long* stamps;  // diagnostic builds only (in-kernel s_memtime stamps)
   // sparse beta source: with bpar_s > 1 the old C (output rows = NHWC pixels of an
   // [*, H, W] image, W = div_bpw.d, H = div_bph.d) holds values only at pixels whose h and w
   // are multiples of bpar_s -- the others are implicit zeros, never read (a strided 1x1
@@ -285,12 +284,8 @@ __device__ __forceinline__ int xcd_remap(int bid, int nblk) {
 // being fetched once per XCD.  Without it the tiles of a split land on different XCDs.
 // host: CLOUD_AMD_SPLIT_XCD=0 keeps the tile-only XCD remap on split-K grids (A/B runs)
 inline int split_xcd_enabled() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("CLOUD_AMD_SPLIT_XCD");
-    v = (e && e[0] == '0') ? 0 : 1;
-  }
-  return v;
+  static const bool on = env_switch("CLOUD_AMD_SPLIT_XCD", true);
+  return on;
 }
 
 struct BlkPos {
@@ -303,6 +298,34 @@ __device__ __forceinline__ BlkPos blk_pos(const CoreParams& P) {
   return {lid % nt, lid / nt};
 }
 __device__ __forceinline__ int blk_split(const CoreParams& P) { return blk_pos(P).split; }
+
+// Barrier and counted waits of the 512-thread cores (ca_gemm256p8.h, ca_gemm_prw.h)
+__device__ __forceinline__ void bar256() {
+  __builtin_amdgcn_s_barrier();
+  asm volatile("" ::: "memory");
+}
+
+template <int N>
+__device__ __forceinline__ void vm_wait() {
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+
+__device__ __forceinline__ void lgkm_wait0() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
+
+// Tile walk of the persistent / data-parallel 256 cores.  Tiles are dealt to XCDs in
+// contiguous ranges (xcd_remap), and inside a range they run in groups of GM tile rows,
+// column-major within the group, so the blocks of one XCD share A row panels and B
+// column panels in their L2.
+__device__ __forceinline__ void tile256_coords(int id, int tiles_m, int tiles_n, int& tm, int& tn) {
+  constexpr int GM = 4;
+  const int per_group = GM * tiles_n;
+  const int g = id / per_group;
+  const int first_m = g * GM;
+  const int rows = (tiles_m - first_m) < GM ? (tiles_m - first_m) : GM;
+  const int r = id - g * per_group;
+  tm = first_m + r % rows;
+  tn = r / rows;
+}
 
 __device__ __forceinline__ s8v zero8() { return s8v{0, 0, 0, 0, 0, 0, 0, 0}; }
 __device__ __forceinline__ s8v ld16(const bf16_t* p) { return *reinterpret_cast<const s8v*>(p); }
@@ -931,28 +954,23 @@ struct loader_stateful<L, decltype((void)&L::advance)> {
 };
 
 template <int BM, int BN, int WM, int WN, template <int, int, int> class LAT, template <int, int, int> class LBT,
-          int EPI, int NSTAGE = 1, int EPF = 1>
+          int EPI, int EPF = 1>
 __device__ __forceinline__ void mfma_gemm_glds(const CoreParams& P) {
-  // Measured on MI355X (bench/conv_shapes.py, bench/gemm_core_ab.py): NSTAGE 1 at
-  // 4 blocks/CU beats NSTAGE 2 at 2 blocks/CU by 10-15% on every ResNet/BERT shape.
-  // NSTAGE 1: load -> wait -> barrier -> MFMA -> barrier; latency hidden by ~4
-  //           co-resident blocks (34 KB LDS each).
-  // NSTAGE 2: the DMA of K tile t+1 is in flight while tile t is multiplied; a
-  //           counted s_waitcnt vmcnt(loads per tile) retires exactly tile t and
-  //           RAW s_barriers (not __syncthreads, whose fence would drain the
-  //           in-flight DMA with vmcnt(0)) order the LDS image.
+  // One LDS stage: load -> wait -> barrier -> MFMA -> barrier; latency hidden by ~4
+  // co-resident blocks (34 KB LDS each).  Measured on MI355X (bench/conv_shapes.py,
+  // bench/gemm_core_ab.py): a two-stage form (the DMA of K tile t+1 in flight under tile t's
+  // MFMAs) at half the resident blocks was 10-15% slower on every ResNet/BERT shape.
   constexpr int NT = WM * WN * 64;
   constexpr int FM = BM / WM / 16, FN = BN / WN / 16;
   constexpr int A_ELEMS = BM * BK, B_ELEMS = BN * BK;
   constexpr int STAGE = A_ELEMS + B_ELEMS;
   constexpr int EPI_LD = EpiLayout<BN>::LD;
-  constexpr int SMEM = (NSTAGE * STAGE > BM * EPI_LD ? NSTAGE * STAGE : BM * EPI_LD);
+  constexpr int SMEM = (STAGE > BM * EPI_LD ? STAGE : BM * EPI_LD);
   constexpr int CPA = A_ELEMS / 8 / NT, CPB = B_ELEMS / 8 / NT;
   using LA = LAT<BM, CPA, NT>;
   using LB = LBT<BN, CPB, NT>;
   constexpr bool A_KC = LA::KC, B_KC = LB::KC;
   static_assert(A_ELEMS % (8 * NT) == 0 && B_ELEMS % (8 * NT) == 0, "tile chunks must divide threads");
-  static_assert(CPA + CPB < 64, "vmcnt range");
   __shared__ __attribute__((aligned(16))) short smem[SMEM];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1023,28 +1041,12 @@ __device__ __forceinline__ void mfma_gemm_glds(const CoreParams& P) {
   };
 
   init_acc();
-  if constexpr (NSTAGE == 1) {
-    for (int t = 0; t < nk; ++t) {
-      issue(t, smem);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      compute(smem);
-      __syncthreads();
-    }
-  } else {
-    if (nk > 0) issue(0, smem);
-    for (int t = 0; t < nk; ++t) {
-      if (t + 1 < nk) {
-        issue(t + 1, smem + ((t + 1) & 1) * STAGE);
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(CPA + CPB) : "memory");
-      } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      }
-      __builtin_amdgcn_s_barrier();
-      compute(smem + (t & 1) * STAGE);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-    }
+  for (int t = 0; t < nk; ++t) {
+    issue(t, smem);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    compute(smem);
+    __syncthreads();
   }
   gemm_epilogue<BM, BN, WM, WN, EPI, SMEM, EPF, FM, FN, false, BIAS0>(P, acc, smem, m0, n0, tm, tid);
 }

@@ -748,15 +748,7 @@ struct GConvDgradSBT {
 template <int BM, int BN, template <int, int, int> class LA, template <int, int, int> class LB, int EPI,
           int EPF = 1>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) conv_glds_kernel(CoreParams P) {
-  mfma_gemm_glds<BM, BN, 2, 2, LA, LB, EPI, 1, EPF>(P);
-}
-
-// 8 waves (2 x 4, wave tile 64 x BN/4) with a double-buffered LDS-DMA pipeline:
-// same 16 waves/CU occupancy as the 4-wave single-stage kernel, but the next K
-// tile's DMA overlaps this tile's MFMAs (CLOUD_AMD_GEMM_CORE=glds8).
-template <int BM, int BN, template <int, int, int> class LA, template <int, int, int> class LB, int EPI>
-__global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) conv_glds8_kernel(CoreParams P) {
-  mfma_gemm_glds<BM, BN, 2, 4, LA, LB, EPI, 2>(P);
+  mfma_gemm_glds<BM, BN, 2, 2, LA, LB, EPI, EPF>(P);
 }
 
 // Tall tiles for the <= 64-channel implicit-GEMM convolutions (ResNet layer-1 3x3 fwd and
@@ -766,62 +758,44 @@ template <int BM, int BN, int WM, int WN, template <int, int, int> class LA, tem
           int EPI, int EPF = 1>
 __global__ void __launch_bounds__(WM * WN * 64) __attribute__((amdgpu_waves_per_eu(4)))
 conv_glds_w_kernel(CoreParams P) {
-  mfma_gemm_glds<BM, BN, WM, WN, LA, LB, EPI, 1, EPF>(P);
+  mfma_gemm_glds<BM, BN, WM, WN, LA, LB, EPI, EPF>(P);
 }
 
 // Forward convolutions with the BN-statistics epilogue read 2 staged rows per epilogue trip
 // (fwd3x3 -2..-5 % per call, end-to-end neutral: 14,148 vs 14,137 img/s same box);
 // CLOUD_AMD_CONV_EPI_PF=0 restores one row per trip (A/B runs).
 bool conv_epi_pf() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("CLOUD_AMD_CONV_EPI_PF");
-    v = (e && e[0] == '0') ? 0 : 1;
-  }
-  return v != 0;
+  static const bool on = env_switch("CLOUD_AMD_CONV_EPI_PF", true);
+  return on;
 }
 
 // CLOUD_AMD_CONV_TALL=0 keeps 128 x 64 tiles on those convolutions (A/B runs).
 bool tall_tiles() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("CLOUD_AMD_CONV_TALL");
-    v = (e && e[0] == '0') ? 0 : 1;
-  }
-  return v != 0;
+  static const bool on = env_switch("CLOUD_AMD_CONV_TALL", true);
+  return on;
 }
 
 // The space-to-depth stem (K = 3 row tiles, N = 64) on the tall 256 x 64 tiles as well: 0.88 ->
 // 0.72 ms per call at b1024 (profiles/r4_s34/); CLOUD_AMD_STEM_TALL=0 keeps 128 x 64 (A/B runs)
 bool stem_tall() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("CLOUD_AMD_STEM_TALL");
-    v = (e && e[0] == '0') ? 0 : 1;
-  }
-  return v != 0;
+  static const bool on = env_switch("CLOUD_AMD_STEM_TALL", true);
+  return on;
 }
 
-// CLOUD_AMD_GEMM_CORE=reg selects the register-staged core (A/B comparisons).
-// 0 = register-staged, 1 = glds single stage (4 waves), 2 = glds double-buffered (8 waves)
-int core_kind() {
-  static int v = -1;
-  if (v < 0) {
+// CLOUD_AMD_GEMM_CORE=reg selects the register-staged core (A/B comparisons); every other
+// value keeps the single-stage LDS-DMA core.
+bool use_glds() {
+  static const bool glds = [] {
     const char* e = getenv("CLOUD_AMD_GEMM_CORE");
-    v = !e ? 1 : (e[0] == 'r' ? 0 : (strcmp(e, "glds8") == 0 ? 2 : 1));
-  }
-  return v;
+    return !(e && e[0] == 'r');
+  }();
+  return glds;
 }
-bool use_glds() { return core_kind() != 0; }
 
 // CLOUD_AMD_TAPMASK=0 keeps the general gather loaders on every convolution (A/B runs).
 bool tapmask_loaders() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("CLOUD_AMD_TAPMASK");
-    v = (e && e[0] == '0') ? 0 : 1;
-  }
-  return v != 0;
+  static const bool on = env_switch("CLOUD_AMD_TAPMASK", true);
+  return on;
 }
 
 template <int BM, int BN, template <int, int, int> class LA, template <int, int, int> class LB, int EPI>
@@ -835,11 +809,6 @@ int launch(const CoreParams& p0, int splits, hipStream_t s) {
   CoreParams p = p0;
   p.split_xcd = split_xcd_enabled();
   const int tiles = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
-  if (BN == 128 && core_kind() == 2) {
-    conv_glds8_kernel<BM, BN, GA, GB, EPI><<<dim3(tiles, 1, splits), 512, 0, s>>>(p);
-    CA_LAUNCH_CHECK();
-    return 0;
-  }
   if constexpr (EPI == EPI_BF16_ST) {
     if (use_glds() && conv_epi_pf()) {
       conv_glds_kernel<BM, BN, GA, GB, EPI, 2><<<dim3(tiles, 1, splits), 256, 0, s>>>(p);
@@ -861,7 +830,7 @@ int launch(const CoreParams& p0, int splits, hipStream_t s) {
 template <template <int, int, int> class LA, template <int, int, int> class LB,
           template <int, int, int> class GA, template <int, int, int> class GB, int EPI>
 int launch_n64(const CoreParams& p0, hipStream_t s) {
-  if (!(tall_tiles() && core_kind() == 1)) return launch<128, 64, LA, LB, GA, GB, EPI>(p0, 1, s);
+  if (!(tall_tiles() && use_glds())) return launch<128, 64, LA, LB, GA, GB, EPI>(p0, 1, s);
   CoreParams p = p0;
   p.split_xcd = split_xcd_enabled();
   const int tiles = (p.M + 255) / 256;
@@ -923,12 +892,8 @@ __global__ void __launch_bounds__(HWG_NT) conv3x3_halo_wgrad_kernel(HaloWgParams
 
 // weight gradient on the halo kernel: CLOUD_AMD_CONV_HALO_WGRAD=0 keeps the implicit GEMM
 bool halo_wgrad_on() {
-  static int en = -1;
-  if (en < 0) {
-    const char* e = getenv("CLOUD_AMD_CONV_HALO_WGRAD");
-    en = (e && e[0] == '0') ? 0 : 1;
-  }
-  return en != 0;
+  static const bool on = env_switch("CLOUD_AMD_CONV_HALO_WGRAD", true);
+  return on;
 }
 
 int halo_launch(const bf16_t* x, const bf16_t* w, bf16_t* y, int Nb, int H, int W, float* stats, const bf16_t* bnz,
@@ -961,12 +926,8 @@ __global__ void __launch_bounds__(STEM_NT) conv_stem_s2d_kernel(StemParams P) {
 }
 
 bool stem_lds_on() {
-  static int en = -1;
-  if (en < 0) {
-    const char* e = getenv("CLOUD_AMD_STEM_LDS");
-    en = (e && e[0] == '0') ? 0 : 1;
-  }
-  return en != 0;
+  static const bool on = env_switch("CLOUD_AMD_STEM_LDS", true);
+  return on;
 }
 
 bool stem_shape(int H, int W, int Cin, int Cout, int KH, int KW, int sh, int sw, int ph, int pw) {

@@ -8,18 +8,18 @@
 // (csrc/include/ca_mfma_core.h) stages K-contiguous tiles for ds_read_b128
 // and M/N-contiguous tiles for the gfx950 transposed read ds_read_b64_tr_b16.
 // Split-K writes fp32 slabs reduced deterministically by splitk_reduce_kernel.
+//
+// Cores, in the order launch<> tries them: the 256 x 256 two-phase core (ca_gemm256p8.h) for
+// large GEMMs, 256 x 96 tiles for forward grids that would end in a partial round, the
+// single-stage LDS-DMA 128 core (ca_mfma_core.h mfma_gemm_glds; with a batched epilogue where
+// it pays), and the register-staged core (CLOUD_AMD_GEMM_CORE=reg).  The persistent
+// resident-weight core (ca_gemm_prw.h) and the transform-A GEMMs (ca_gemm_xa.h) have their own
+// entry points below.  Cores that measured slower and were removed: docs/performance.md.
 #include <stdlib.h>
 #include <string.h>
 
 #include "ca_gemm256p8.h"
 #include "ca_gemm_xa.h"
-
-// Experiment-only cores -- the 8-wave glds8 variant, the 256 x 256 ring core, stream-K and the
-// 256 x 128 variant -- each measured slower than the default dispatch (docs/performance.md) and
-// kept for A/B runs: compiled only with CLOUD_AMD_BUILD_EXPERIMENTAL=1 (-DCA_EXPERIMENTAL=1).
-#ifndef CA_EXPERIMENTAL
-#define CA_EXPERIMENTAL 0
-#endif
 
 namespace {
 using namespace ca;
@@ -37,7 +37,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) d
 // same, with the statistics epilogue reading 4 staged rows ahead of their stores
 template <int BM, int BN, template <int, int, int> class LA, template <int, int, int> class LB, int EPI>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) dense_gemm_glds_pf_kernel(CoreParams P) {
-  mfma_gemm_glds<BM, BN, 2, 2, LA, LB, EPI, 1, 4>(P);
+  mfma_gemm_glds<BM, BN, 2, 2, LA, LB, EPI, 4>(P);
 }
 
 // Forward GEMMs with the BN-statistics epilogue (ResNet 1x1 convs) use the batched
@@ -45,12 +45,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) d
 // b1024 +0.9 %.  Plain bias/activation epilogues (BERT) measured 0.8 % slower with it, so
 // they keep one row per trip.  CLOUD_AMD_EPI_PF=0 turns it off (A/B runs).
 bool epi_pf() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("CLOUD_AMD_EPI_PF");
-    v = (e && e[0] == '0') ? 0 : 1;
-  }
-  return v != 0;
+  static const bool on = env_switch("CLOUD_AMD_EPI_PF", true);
+  return on;
 }
 
 // 256 x 96 tiles for forward GEMMs whose 128 x 128 grid ends in a partial round while the
@@ -61,74 +57,26 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) d
   mfma_gemm_glds<256, 96, 2, 2, GDenseKC, GDenseKC, EPI>(P);
 }
 
-#if CA_EXPERIMENTAL
-// 8 waves (2 x 4, wave tile 64 x BN/4) with a double-buffered LDS-DMA pipeline:
-// same 16 waves/CU occupancy as the 4-wave single-stage kernel, but the next K
-// tile's DMA overlaps this tile's MFMAs (CLOUD_AMD_GEMM_CORE=glds8).
-template <int BM, int BN, template <int, int, int> class LA, template <int, int, int> class LB, int EPI>
-__global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) dense_gemm_glds8_kernel(CoreParams P) {
-  mfma_gemm_glds<BM, BN, 2, 4, LA, LB, EPI, 2>(P);
-}
-#endif  // CA_EXPERIMENTAL
-
-#if CA_EXPERIMENTAL
-// The 256 x 256 ring core (csrc/include/ca_gemm256.h) for large GEMMs: one 512-thread
-// workgroup per CU.  K-contiguous operands use the 32-deep KC32 loader, N-contiguous ones
-// the same GDenseNC loader as the 128 cores.
-template <template <int, int, int> class LA, template <int, int, int> class LB, int EPI>
-__global__ void __launch_bounds__(512) dense_gemm_256_kernel(CoreParams P) {
-  mfma_gemm_256<LA, LB, EPI>(P);
-}
-#endif  // CA_EXPERIMENTAL
-
 // The 256 x 256 x 64 core with two staggered wave groups and two phases per K tile
 // (csrc/include/ca_gemm256p8.h).
 template <template <int, int, int> class LA, template <int, int, int> class LB, int EPI>
 __global__ void __launch_bounds__(512) dense_gemm_256p8_kernel(CoreParams P) {
-  mfma_gemm_256p8<LA, LB, EPI, 2>(P);
+  mfma_gemm_256p8<LA, LB, EPI>(P);
 }
-
-#if CA_EXPERIMENTAL
-// Stream-K form of the same core (ca_gemm256p8.h mfma_gemm_256p8_sk): one workgroup per CU,
-// each an equal range of the (tile, K iteration) space.
-template <template <int, int, int> class LA, template <int, int, int> class LB, int EPI>
-__global__ void __launch_bounds__(512) dense_gemm_256p8_sk_kernel(CoreParams P, SkParams S) {
-  mfma_gemm_256p8_sk<LA, LB, EPI>(P, S);
-}
-
-// Its 256 x 128 single-phase, three-buffer variant (same header).
-template <template <int, int, int> class LA, template <int, int, int> class LB, int EPI>
-__global__ void __launch_bounds__(512) dense_gemm_256x128_kernel(CoreParams P) {
-  mfma_gemm_256x128<LA, LB, EPI>(P);
-}
-#endif  // CA_EXPERIMENTAL
 
 // CLOUD_AMD_GEMM_CORE selects the core (A/B comparisons; ca_gemm_set_core overrides it):
-// 0 "reg" = register-staged, 1 "glds" = glds single stage (4 waves) only, 2 "glds8" = glds
-// double-buffered (8 waves), 3 "glds_ring" = glds plus the 256 x 256 ring core (ca_gemm256.h)
-// for large GEMMs, 4 "v256" = the ring core for every GEMM with M, N >= 256 (tests),
-// 5 (default) = glds plus the 256 x 256 two-phase core (ca_gemm256p8.h) for large GEMMs
-// (use_256 below; 8192^3: ring 1,172-1,183 -> 1,245-1,260 TF/s, split-K / TN weight-gradient
-// layout 1,042 -> 1,142), 6 "vp8" = the two-phase core for every GEMM with M, N >= 256 (tests).
+// 0 "reg" = register-staged, 1 "glds" = glds single stage (4 waves) only, 5 (default, and any
+// other name) = glds plus the 256 x 256 two-phase core (ca_gemm256p8.h) for large GEMMs (use_256
+// below), 6 "vp8" = the two-phase core for every GEMM with M, N >= 256 (tests).  2-4 named
+// removed cores and stay unused, so the integers tests and scripts pass keep their meaning.
 int g_core_kind = -1;
 int core_kind() {
   if (g_core_kind < 0) {
     const char* e = getenv("CLOUD_AMD_GEMM_CORE");
-    g_core_kind = !e ? 5
-                     : (e[0] == 'r' ? 0
-                        : strcmp(e, "glds8") == 0     ? 2
-                        : strcmp(e, "glds") == 0      ? 1
-                        : strcmp(e, "glds_ring") == 0 ? 3
-                        : strcmp(e, "v256") == 0      ? 4
-                        : strcmp(e, "vp8") == 0       ? 6
-                                                      : 5);
+    g_core_kind = !e ? 5 : (e[0] == 'r' ? 0 : strcmp(e, "glds") == 0 ? 1 : strcmp(e, "vp8") == 0 ? 6 : 5);
   }
-#if !CA_EXPERIMENTAL
-  if (g_core_kind >= 2 && g_core_kind <= 4) g_core_kind = 5;  // not built: the default dispatch
-#endif
   return g_core_kind;
 }
-bool core_p8() { return core_kind() == 5 || core_kind() == 6; }
 bool use_glds() { return core_kind() != 0; }
 
 // Persistent resident-weight core (csrc/include/ca_gemm_prw.h) for the small-K forward 1x1
@@ -140,12 +88,8 @@ __global__ void __launch_bounds__(512) prw_gemm_kernel(CoreParams P) {
 
 // CLOUD_AMD_GEMM_PRW=0 keeps these GEMMs on the data-parallel 128 core (A/B runs)
 bool prw_enabled() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("CLOUD_AMD_GEMM_PRW");
-    v = (e && e[0] == '0') ? 0 : 1;
-  }
-  return v != 0;
+  static const bool on = env_switch("CLOUD_AMD_GEMM_PRW", true);
+  return on;
 }
 
 int cu_count() {
@@ -182,12 +126,8 @@ int cu_count() {
 // turnaround of one 8-wave workgroup per CU is).  CLOUD_AMD_GEMM_PRWN=0 keeps them on the tiled
 // cores (A/B runs).
 bool prwn_enabled() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("CLOUD_AMD_GEMM_PRWN");
-    v = (e && e[0] == '0') ? 0 : 1;
-  }
-  return v != 0;
+  static const bool on = env_switch("CLOUD_AMD_GEMM_PRWN", true);
+  return on;
 }
 
 int prw_kind(int M, int N, int K, long lda, long ldb, long ldc, bool stats) {
@@ -377,11 +317,7 @@ static double tile_balance(long tiles) {
 // BERT shapes: QKV (N = 2304) wins; N = 768 (one round of 256 x 96) and N = 3072 (whole
 // 128 rounds) lose (profiles/r5_s9/r5s9_gb.log).  CLOUD_AMD_GEMM_256X96=0 turns it off.
 static bool use_256x96(const CoreParams& p, int splits) {
-  static int en = -1;
-  if (en < 0) {
-    const char* e = getenv("CLOUD_AMD_GEMM_256X96");
-    en = (e && e[0] == '0') ? 0 : 1;
-  }
+  static const bool en = env_switch("CLOUD_AMD_GEMM_256X96", true);
   if (!en || splits != 1 || p.N % 96 || p.M < 4096 || p.stats) return false;
   const long t96 = ((p.M + 255) / 256) * (p.N / 96), t128 = ((p.M + 127) / 128) * ((p.N + 127) / 128);
   return t96 >= 512 && tile_balance(t96) >= 0.999 && tile_balance(t128) < 0.95;
@@ -396,95 +332,12 @@ static bool use_256x96(const CoreParams& p, int splits) {
 // nearly full round of 256 x 256 blocks (ops/raw.py wgrad_into: BERT's FFN / QKV weight
 // gradients = 36 x 7 / 27 x 9 blocks).
 static bool use_256(const CoreParams& p, int splits) {
-  if (core_kind() == 4 || core_kind() == 6) return p.M >= 256 && p.N >= 256;
-  if ((core_kind() != 3 && core_kind() != 5) || p.M < 256 || p.N < 256 || p.k_per_split < 512) return false;
+  if (core_kind() == 6) return p.M >= 256 && p.N >= 256;
+  if (core_kind() != 5 || p.M < 256 || p.N < 256 || p.k_per_split < 512) return false;
   const long t = (long)((p.M + 255) / 256) * ((p.N + 255) / 256) * splits;
   if (splits > 1 && t >= 224 && t <= 256) return true;
   return t >= 256 && (tile_balance(t) >= 0.999 || (t >= 512 && tile_balance(t) >= 0.85));
 }
-
-#if CA_EXPERIMENTAL
-// 256 x 128 tiles where 256 x 256 tiles do not fill whole rounds but 256 x 128 tiles do
-// (BERT-base FFN1 forward / FFN2 input gradient at M = 8192: N = 3072 -> 768 tiles = 3 rounds;
-// 256 x 256 gives 384 = 1.5).  Opt-in (CLOUD_AMD_GEMM_256X128=1): measured 669 vs 830 TF/s for
-// the 128 core on 8192 x 3072 x 768 and BERT 6,286 / 6,328 vs 6,863 / 6,875 seq/s
-// (profiles/r4_s18/) -- one barrier pair per K tile with 16 fragment reads per wave does not
-// keep the MFMA pipe as busy as the two-phase 256 x 256 schedule.
-static bool use_256x128(const CoreParams& p, int splits) {
-  static int en = -1;
-  if (en < 0) {
-    const char* e = getenv("CLOUD_AMD_GEMM_256X128");
-    en = (e && e[0] == '1') ? 1 : 0;
-  }
-  if (!en || !core_p8() || splits != 1 || p.M < 256 || p.N < 128 || p.K < 512) return false;
-  const long t = (long)((p.M + 255) / 256) * ((p.N + 127) / 128);
-  return t >= 256 && (tile_balance(t) >= 0.999 || (t >= 512 && tile_balance(t) >= 0.85));
-}
-
-// Stream-K (ca_gemm256p8.h) for plain bf16-epilogue GEMMs whose 256 x 256 grid is between
-// 3/8 of a round and two rounds of the chip and not whole rounds: BERT-base's M = 8192 forward
-// and input-gradient GEMMs (96-384 tiles).  OFF by default (CLOUD_AMD_GEMM_STREAMK=1: those
-// shapes, =2: wherever the operands allow -- tests): measured slower than the 128 x 128 core
-// it would replace on every BERT shape (bin/gemm_bench, profiles/r5_s4/: QKV forward 57.4 vs
-// 42.1 us, FFN2 forward 75.0 vs 59.8, attention output 48.4 vs 19.6) and BERT 5,365 vs 6,866
-// seq/s -- the two-phase core's per-iteration rate on short segments plus one 256-KB fp32
-// partial store and load per split tile cost more than the last round's idle CUs.
-static int g_streamk = -1;
-static int streamk_mode() {
-  if (g_streamk < 0) {
-    const char* e = getenv("CLOUD_AMD_GEMM_STREAMK");
-    g_streamk = e ? atoi(e) : 0;
-  }
-  return g_streamk;
-}
-
-static bool use_streamk(const CoreParams& p, int splits) {
-  const int mode = streamk_mode();
-  if (!mode || !core_p8() || splits != 1 || p.M < 256 || p.N < 256 || p.stats || p.K < 2 * BK) return false;
-  if (mode == 2) return true;
-  const long t = (long)((p.M + 255) / 256) * ((p.N + 255) / 256);
-  const long cus = cu_count();
-  return t * 8 >= cus * 3 && t < 2 * cus && tile_balance(t) < 0.999;
-}
-
-// Per-stream stream-K workspace: cu_count() fp32 partial tiles (256 KB each) and the tile
-// tickets (+1 error word), allocated once per stream and zeroed once -- the owners leave
-// their tickets at zero for the next launch, which is ordered after this one on the stream.
-struct SkWorkspace {
-  float* part = nullptr;
-  int* ticket = nullptr;
-  int nticket = 0;
-};
-
-static int streamk_workspace(hipStream_t s, int tiles, SkParams& S) {
-  static SkWorkspace slots[8];
-  static hipStream_t keys[8];
-  static int used = 0;
-  int k = 0;
-  while (k < used && keys[k] != s) ++k;
-  if (k == used) {
-    if (used == 8) return -4;
-    keys[used++] = s;
-  }
-  SkWorkspace& w = slots[k];
-  if (!w.part && hipMalloc(&w.part, (size_t)cu_count() * 256 * 256 * 4) != hipSuccess) return -5;
-  if (w.nticket < tiles + 1) {
-    if (w.ticket) {
-      hipStreamSynchronize(s);  // the old tickets may still be in use by a queued launch
-      hipFree(w.ticket);
-    }
-    const int n = tiles + 1 > 1024 ? tiles + 1 : 1024;
-    if (hipMalloc(&w.ticket, (size_t)n * 4) != hipSuccess) return -5;
-    hipMemsetAsync(w.ticket, 0, (size_t)n * 4, s);
-    w.nticket = n;
-  }
-  S.part = w.part;
-  S.ticket = w.ticket;
-  S.err_index = w.nticket - 1;
-  return 0;
-}
-
-#endif  // CA_EXPERIMENTAL
 
 template <int BM, int BN, template <int, int, int> class LA, template <int, int, int> class LB,
           template <int, int, int> class GA, template <int, int, int> class GB, int EPI>
@@ -496,61 +349,19 @@ int launch(const CoreParams& p0, int splits, hipStream_t s) {
   // (ca_mfma_core.h BUF_CAP): rows of a tile (KC) or one split's K range (NC)
   const long span = (long)(p.k_per_split + BK > 256 ? p.k_per_split + BK : 256) * (p.lda > p.ldb ? p.lda : p.ldb) * 2;
   if (use_glds() && span >= (long)BUF_CAP) return -3;
-#if CA_EXPERIMENTAL
-  if constexpr (BM == 128 && BN == 128 && EPI == EPI_BF16) {
-    if (use_streamk(p, splits)) {
-      SkParams S{};
-      const int t256 = ((p.M + 255) / 256) * ((p.N + 255) / 256);
-      const int rc = streamk_workspace(s, t256, S);
-      if (rc) return rc;
-      S.ipt = (p.K + BK - 1) / BK;
-      S.total = t256 * S.ipt;
-      // every range non-empty: an empty one would be counted as a contributor by the owner
-      const int nwg = (int)(S.total < cu_count() ? S.total : cu_count());
-      constexpr bool AK = GA<BM, 1, 256>::KC, BKC = GB<BN, 1, 256>::KC;
-      if constexpr (AK && BKC)
-        dense_gemm_256p8_sk_kernel<GDenseKC, GDenseKC, EPI><<<nwg, 512, 0, s>>>(p, S);
-      else if constexpr (AK && !BKC)
-        dense_gemm_256p8_sk_kernel<GDenseKC, GDenseNC, EPI><<<nwg, 512, 0, s>>>(p, S);
-      else if constexpr (!AK && !BKC)
-        dense_gemm_256p8_sk_kernel<GDenseNC, GDenseNC, EPI><<<nwg, 512, 0, s>>>(p, S);
-      else
-        return -2;
-      CA_LAUNCH_CHECK();
-      return 0;
-    }
-  }
-#endif  // CA_EXPERIMENTAL
   if constexpr (BM == 128 && BN == 128 && (EPI == EPI_BF16 || EPI == EPI_F32_PARTIAL || EPI == EPI_BF16_ST)) {
     if (use_256(p, splits)) {
       const int t256 = ((p.M + 255) / 256) * ((p.N + 255) / 256);
       constexpr bool AK = GA<BM, 1, 256>::KC, BKC = GB<BN, 1, 256>::KC;
-      if (core_p8()) {
-        if constexpr (AK && BKC)
-          dense_gemm_256p8_kernel<GDenseKC, GDenseKC, EPI><<<dim3(t256, 1, splits), 512, 0, s>>>(p);
-        else if constexpr (AK && !BKC)
-          dense_gemm_256p8_kernel<GDenseKC, GDenseNC, EPI><<<dim3(t256, 1, splits), 512, 0, s>>>(p);
-        else if constexpr (!AK && !BKC)
-          dense_gemm_256p8_kernel<GDenseNC, GDenseNC, EPI><<<dim3(t256, 1, splits), 512, 0, s>>>(p);
-        else
-          return -2;
-        CA_LAUNCH_CHECK();
-        return 0;
-      }
-#if CA_EXPERIMENTAL
+      static_assert(AK || !BKC, "no layout pairs an M-contiguous A with a K-contiguous B");
       if constexpr (AK && BKC)
-        dense_gemm_256_kernel<GDenseKC32, GDenseKC32, EPI><<<dim3(t256, 1, splits), 512, 0, s>>>(p);
+        dense_gemm_256p8_kernel<GDenseKC, GDenseKC, EPI><<<dim3(t256, 1, splits), 512, 0, s>>>(p);
       else if constexpr (AK && !BKC)
-        dense_gemm_256_kernel<GDenseKC32, GDenseNC, EPI><<<dim3(t256, 1, splits), 512, 0, s>>>(p);
+        dense_gemm_256p8_kernel<GDenseKC, GDenseNC, EPI><<<dim3(t256, 1, splits), 512, 0, s>>>(p);
       else if constexpr (!AK && !BKC)
-        dense_gemm_256_kernel<GDenseNC, GDenseNC, EPI><<<dim3(t256, 1, splits), 512, 0, s>>>(p);
-      else
-        return -2;
+        dense_gemm_256p8_kernel<GDenseNC, GDenseNC, EPI><<<dim3(t256, 1, splits), 512, 0, s>>>(p);
       CA_LAUNCH_CHECK();
       return 0;
-#else
-      return -2;  // unreachable: without the experimental build core_p8() holds whenever use_256 does
-#endif
     }
     if constexpr (EPI == EPI_BF16 && GA<BM, 1, 256>::KC && GB<BN, 1, 256>::KC) {
       if (use_glds() && use_256x96(p, splits)) {
@@ -560,28 +371,7 @@ int launch(const CoreParams& p0, int splits, hipStream_t s) {
         return 0;
       }
     }
-#if CA_EXPERIMENTAL
-    if (use_256x128(p, splits)) {
-      const int t = ((p.M + 255) / 256) * ((p.N + 127) / 128);
-      constexpr bool AK = GA<BM, 1, 256>::KC, BKC = GB<BN, 1, 256>::KC;
-      if constexpr (AK && BKC)
-        dense_gemm_256x128_kernel<GDenseKC, GDenseKC, EPI><<<dim3(t, 1, 1), 512, 0, s>>>(p);
-      else if constexpr (AK && !BKC)
-        dense_gemm_256x128_kernel<GDenseKC, GDenseNC, EPI><<<dim3(t, 1, 1), 512, 0, s>>>(p);
-      else
-        return -2;
-      CA_LAUNCH_CHECK();
-      return 0;
-    }
-#endif  // CA_EXPERIMENTAL
   }
-#if CA_EXPERIMENTAL
-  if (BN == 128 && core_kind() == 2) {
-    dense_gemm_glds8_kernel<BM, BN, GA, GB, EPI><<<dim3(tiles, 1, splits), 512, 0, s>>>(p);
-    CA_LAUNCH_CHECK();
-    return 0;
-  }
-#endif
   // K-contiguous operands only (forward GEMMs): the N-contiguous loaders' extra registers
   // make the batched epilogue spill (448-480 B/lane of scratch)
   // Dense-layer epilogues that read memory (act' source, old C for beta) or run the
@@ -610,7 +400,6 @@ int launch(const CoreParams& p0, int splits, hipStream_t s) {
   return 0;
 }
 
-
 // 128-wide N tiles unless N is small, or the 128-wide grid would leave a badly
 // filled last round (e.g. M=8192, N=768: 384 tiles -> 1.5 rounds) and halving
 // the tile width balances it (768 tiles -> 3 full rounds).
@@ -634,17 +423,6 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) x
   mfma_gemm_xa<BM, BN, BKC, EPI, XM, 512>(P, X);
 }
 
-#if CA_EXPERIMENTAL
-// 128 x 256 tiles on 8 waves (2 x 4, wave tile 64 x 64): one workgroup per CU (64 accumulator
-// registers per lane on top of the 128 x 128 form's staging).  Measured slower than the 16-wave
-// forms (docs/performance.md, round 6): experiment-only (CLOUD_AMD_XA_N256=2)
-template <int BM, int BN, bool BKC, int EPI, int XM>
-__global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) xa_gemm8w_kernel(CoreParams P,
-                                                                                               XaParams X) {
-  mfma_gemm_xa<BM, BN, BKC, EPI, XM, 512>(P, X);
-}
-#endif
-
 // the same tiles with two K tiles' raw operands in flight (coefficients staged in LDS)
 template <int BN, bool BKC, int EPI, int XM>
 __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4))) xa_gemm16d_kernel(CoreParams P,
@@ -666,26 +444,22 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4))) 
 // ... and the 128 x 64 ones (stage 1; CLOUD_AMD_XA_WAVES_N64=0: 4 waves): 85-108 registers;
 // 14,775 / 14,784 / 14,767 -> 14,874 / 14,796 / 14,826 img/s interleaved (profiles/r4_s22/)
 static bool xa_waves8_n64() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("CLOUD_AMD_XA_WAVES_N64");
-    v = (e && e[0] == '0') ? 0 : 1;
-  }
-  return v != 0;
+  static const bool on = env_switch("CLOUD_AMD_XA_WAVES_N64", true);
+  return on;
 }
 // CLOUD_AMD_XA_N256: transform-A GEMMs with N a multiple of 256 (ResNet-50 stages 3-4: bn3 ->
 // conv3 dgrad, bn3 -> next conv1 at N = 256 / 512) on 128 x 256 tiles, so each A tile is read
 // and BN-transformed once per 256 columns instead of once per 128.  1: 16-wave workgroups (wave
-// tile 64 x 32, <= 128 registers: one per CU); 2: 8 waves (64 x 64, ~190 registers: one per CU
-// at half the waves; CLOUD_AMD_BUILD_EXPERIMENTAL builds only); 3 (default): 16 waves with two K
-// tiles in flight (mfma_gemm_xa_deep, K <= 2048; else form 1); 0: off (128 x 128 tiles).  The
+// tile 64 x 32, <= 128 registers: one per CU); 3 (default, and any other value): 16 waves with
+// two K tiles in flight (mfma_gemm_xa_deep, K <= 2048; else form 1); 0: off (128 x 128 tiles).
+// (2 named a removed 8-wave form, docs/performance.md round 6.)  The
 // two-BN residual epilogue (EPI_BF16_BNR2) keeps the 128-wide tiles: its three statistics rows do
 // not fit the 16-wave LDS image.
 int g_xa_n256 = -1;
 static int xa_n256() {
   if (g_xa_n256 < 0) {
     const char* e = getenv("CLOUD_AMD_XA_N256");
-    g_xa_n256 = (e && e[0] >= '0' && e[0] <= '3') ? e[0] - '0' : 3;
+    g_xa_n256 = (e && (e[0] == '0' || e[0] == '1')) ? e[0] - '0' : 3;
   }
   return g_xa_n256;
 }
@@ -763,25 +537,19 @@ int xa_launch(const CoreParams& p0, const XaParams& x, hipStream_t s) {
   p.split_xcd = 0;
   const int tm = (p.M + 127) / 128;
   const int n256 = p.N % 256 == 0 ? xa_n256() : 0;
-  bool w16 = false;
   if constexpr (EPI != EPI_BF16_BNR2) {  // three 16-wave statistics rows do not fit its LDS image
     if (n256 == 3 && p.K <= XA_DEEP_KMAX) {
       xa_gemm16d_kernel<256, LB, EPI, XM><<<tm * (p.N / 256), 1024, 0, s>>>(p, x);
-      w16 = true;
-    } else if (n256 == 1 || n256 == 3) {
+      CA_LAUNCH_CHECK();
+      return 0;
+    }
+    if (n256 == 1 || n256 == 3) {
       xa_gemm16_kernel<128, 256, LB, EPI, XM><<<tm * (p.N / 256), 1024, 0, s>>>(p, x);
-      w16 = true;
+      CA_LAUNCH_CHECK();
+      return 0;
     }
   }
-  bool w8w = false;
-#if CA_EXPERIMENTAL
-  if (!w16 && n256 == 2) {
-    xa_gemm8w_kernel<128, 256, LB, EPI, XM><<<tm * (p.N / 256), 512, 0, s>>>(p, x);
-    w8w = true;
-  }
-#endif
-  if (w16 || w8w) {
-  } else if (want_small_n(p, 1)) {
+  if (want_small_n(p, 1)) {
     bool w8 = false;
     if constexpr (EPI != EPI_BF16_BNR2) {  // its three statistics rows do not fit the 8-wave LDS image
       if (xa_waves8() && xa_waves8_n64()) {
@@ -806,12 +574,7 @@ int xa_launch(const CoreParams& p0, const XaParams& x, hipStream_t s) {
 
 template <int EPI>
 int dispatch(int layout, const CoreParams& p, int splits, hipStream_t s) {
-  // stream-K runs on 256 x 256 tiles whatever the 128-tile grid's balance (launch<128, 128>)
-#if CA_EXPERIMENTAL
-  const bool small_n = !(EPI == EPI_BF16 && use_streamk(p, splits)) && want_small_n(p, splits);
-#else
   const bool small_n = want_small_n(p, splits);
-#endif
   switch (layout) {
     case 0:
       return small_n ? launch<128, 64, DenseKC, DenseKC, GDenseKC, GDenseKC, EPI>(p, splits, s)
@@ -848,26 +611,11 @@ int ca_dgrad_gemm(int layout, const bf16_t* A, long lda, const bf16_t* B, long l
                   int par_s, int par_h, int par_w);
 
 // Select the GEMM core for this process (values as CLOUD_AMD_GEMM_CORE above); returns
-// the previous one.
-// Stream-K mode (CLOUD_AMD_GEMM_STREAMK: 0 off, 1 auto, 2 wherever allowed); returns the previous.
-// -1: stream-K is not in this build (CLOUD_AMD_BUILD_EXPERIMENTAL=1 builds it)
-int ca_gemm_set_streamk(int mode) {
-#if CA_EXPERIMENTAL
-  const int prev = streamk_mode();
-  if (mode >= 0 && mode <= 2) g_streamk = mode;
-  return prev;
-#else
-  (void)mode;
-  return -1;
-#endif
-}
-
-int ca_gemm_experimental_built() { return CA_EXPERIMENTAL; }
-
-// -1: the requested core is not in this build (kinds 2-4 need CLOUD_AMD_BUILD_EXPERIMENTAL=1)
+// the previous one (any other value, e.g. -1, only reads it).
+// -1: kinds 2-4 named cores that no longer exist; nothing changes
 int ca_gemm_set_core(int kind) {
   const int prev = core_kind();
-  if (!CA_EXPERIMENTAL && kind >= 2 && kind <= 4) return -1;
+  if (kind >= 2 && kind <= 4) return -1;
   if (kind >= 0 && kind <= 6) g_core_kind = kind;
   return prev;
 }
@@ -875,7 +623,7 @@ int ca_gemm_set_core(int kind) {
 // Transform-A tiles for N % 256 == 0 (values as CLOUD_AMD_XA_N256); returns the previous mode.
 int ca_gemm_set_xa_n256(int mode) {
   const int prev = xa_n256();
-  if (mode == 2 && !CA_EXPERIMENTAL) return -1;  // the 8-wave form is experiment-only
+  if (mode == 2) return -1;  // named a removed 8-wave form
   if (mode >= 0 && mode <= 3) g_xa_n256 = mode;
   return prev;
 }

@@ -1,5 +1,5 @@
 """Which ResNet gradient slots differ between the transform-A tile modes (CLOUD_AMD_XA_N256
-0 / 1 / 2) with every BN fold site on?  Diagnostic for the 128 x 256 tiles."""
+0 / 1 / 3) with every BN fold site on?  Diagnostic for the 128 x 256 tiles."""
 import os
 import sys
 
@@ -30,7 +30,7 @@ def grads(mode):
 
 
 g0, names = grads(0)
-for mode in (1, 2):
+for mode in (1, 3):
     g1, _ = grads(mode)
     for ai, (x, y) in enumerate(zip(g1, g0)):
         bad = [(n, k, float((x[o:o + k].float() - y[o:o + k].float()).abs().max())) for n, o, k in names[ai]

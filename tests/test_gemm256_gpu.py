@@ -1,25 +1,23 @@
-"""The 256 x 256 GEMM cores -- the ring core (csrc/include/ca_gemm256.h, core kind 4 = v256)
-and the 8-phase core (csrc/include/ca_gemm256p8.h, core kind 6 = vp8), each forced on every
-GEMM with M, N >= 256 -- against a plain PyTorch fp32
+"""The 256 x 256 two-phase GEMM core (csrc/include/ca_gemm256p8.h, core kind 6 = vp8) forced on
+every GEMM with M, N >= 256 -- against a plain PyTorch fp32
 GEMM of the same bf16 operands: forward (NT), input grad (NN), weight grad (TN, split-K fp32
 slabs), the fused bias + activation and BN-statistics epilogues, ragged M / N / K (partial
 tiles, K tails read as zeros through the buffer range check), one to many K tiles -- plus
-the default dispatch (core kind 3) on a shape that selects the 256 core by itself."""
+the default dispatch (core kind 5) on a shape that selects the 256 core by itself, and the core
+kinds and transform-A mode that no longer exist."""
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(params=[4, 6], ids=["ring256", "p8"])
+@pytest.fixture(params=[6], ids=["p8"])
 def core256(request):
-    """Force a 256 x 256 core on every GEMM with M, N >= 256: 4 = the ring core (v256),
-    6 = the 8-phase core (vp8, csrc/include/ca_gemm256p8.h)."""
+    """Force the 256 x 256 two-phase core (6 = vp8, csrc/include/ca_gemm256p8.h) on every GEMM
+    with M, N >= 256."""
     from cloud_amd.ops import _ext
 
     ext = _ext.load(required=True)
-    if request.param == 4 and not ext.experimental_built():
-        pytest.skip("ring core: experiment-only, built with CLOUD_AMD_BUILD_EXPERIMENTAL=1")
     prev = ext.gemm_set_core(request.param)
     assert prev >= 0
     yield request.param
@@ -95,36 +93,22 @@ def test_default_dispatch_selects_256_on_large_gemm():
         ext.gemm_set_core(prev)
 
 
-@pytest.mark.parametrize("M,N,K", [(8192, 3072, 768), (8000, 1000, 704), (4096, 2048, 4096)])
-def test_256x128_core_dispatch(M, N, K, monkeypatch):
-    """The 256 x 128 single-phase core (ca_gemm256p8.h mfma_gemm_256x128, opt-in with
-    CLOUD_AMD_GEMM_256X128=1, read once per process -- so this test also covers whatever the
-    process decided) where 256 x 128 tiles fill whole rounds (BERT FFN1 forward / FFN2 input
-    gradient shape first; ragged M / N / K): forward with bias + GELU + pre-activation, input
-    gradient with GELU' -- against fp32 references."""
+def test_removed_core_kinds_are_rejected():
+    """Core kinds 2-4 and transform-A mode 2 named experiment-only cores that are gone:
+    selecting one returns -1 and leaves the active kind alone (gemm_set_core(-1) only reads
+    it), and the default dispatch still computes a ragged GEMM (partial M and N tiles, K tail)."""
     from cloud_amd.ops import _ext, raw
 
-    if not _ext.load(required=True).experimental_built():
-        pytest.skip("256 x 128 core: experiment-only, built with CLOUD_AMD_BUILD_EXPERIMENTAL=1")
-    monkeypatch.setenv("CLOUD_AMD_GEMM_256X128", "1")
-
+    ext = _ext.load(required=True)
+    kind = ext.gemm_set_core(-1)
+    for k in (2, 3, 4):
+        assert ext.gemm_set_core(k) == -1
+        assert ext.gemm_set_core(-1) == kind
+    assert ext.gemm_set_xa_n256(2) == -1
+    M, N, K = 300, 264, 200
     torch.manual_seed(M + N + K)
     a = torch.randn(M, K, device="cuda").to(torch.bfloat16)
-    w = (torch.randn(N, K, device="cuda") * 0.05).to(torch.bfloat16)
-    b = torch.randn(N, device="cuda") * 0.1
-    pre = torch.empty(M, N, device="cuda", dtype=torch.bfloat16)
-    y = raw.gemm(a, w, bias=b, act="gelu", preact=pre)
-    ref = a.float() @ w.float().t() + b
-    assert _rel(pre, ref) < 5e-3
-    assert _rel(y, torch.nn.functional.gelu(pre.float())) < 1e-2
-    w2 = (torch.randn(K, N, device="cuda") * 0.05).to(torch.bfloat16)  # NN: dx[M, N] = dy[M, K] @ w2[K, N]
-    dy = torch.randn(M, K, device="cuda").to(torch.bfloat16)
-    dx = raw.gemm(dy, w2, layout=raw.NN, act="gelu", dact_src=pre)
-    ref2 = (dy.float() @ w2.float()) * _gelu_grad(pre.float())
-    assert _rel(dx, ref2) < 1e-2, _rel(dx, ref2)
-
-
-def _gelu_grad(x):
-    cdf = 0.5 * (1.0 + torch.erf(x / 2 ** 0.5))
-    pdf = torch.exp(-0.5 * x * x) / (2 * torch.pi) ** 0.5
-    return cdf + x * pdf
+    w = torch.randn(N, K, device="cuda").to(torch.bfloat16)
+    assert _rel(raw.gemm(a, w), a.float() @ w.float().t()) < 5e-3
+    dy = torch.randn(M, N, device="cuda").to(torch.bfloat16)
+    assert _rel(raw.gemm(dy, w, layout=raw.NN), dy.float() @ w.float()) < 5e-3

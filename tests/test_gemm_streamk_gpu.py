@@ -1,4 +1,8 @@
-"""Stream-K GEMM (csrc/include/ca_gemm256p8.h mfma_gemm_256p8_sk): one workgroup per CU over
+"""The stream-K core was removed (numbers in docs/performance.md); its tests below skip and are
+deleted in a follow-up change, which also moves test_streamk_bert_dense_epilogues -- it runs on the
+default dispatch -- into tests/test_gemm256_gpu.py.  What they covered:
+
+Stream-K GEMM (mfma_gemm_256p8_sk): one workgroup per CU over
 all (256 x 256 tile, K iteration) pairs; a tile split across workgroups is finished by its
 owner, which adds the other contributors' fp32 partial tiles in a fixed order behind an
 agent-scope ticket.  Against plain PyTorch fp32 GEMMs of the same bf16 operands: forward (NT)
@@ -18,7 +22,7 @@ def streamk():
 
     ext = _ext.load(required=True)
     if not ext.experimental_built():
-        pytest.skip("stream-K: experiment-only, built with CLOUD_AMD_BUILD_EXPERIMENTAL=1")
+        pytest.skip("stream-K core removed; test kept until its file is deleted")
     prev = ext.gemm_set_streamk(2)  # wherever the operands allow
     yield ext
     ext.gemm_set_streamk(prev)
