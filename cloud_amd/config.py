@@ -128,6 +128,10 @@ _VARS = [
         "stage 1) forward and input gradient on the LDS-resident kernel (ca_conv_halo.h: input patch and all 9 taps "
         "in LDS, persistent grid); 0 = implicit-GEMM tiles, 2 = halo kernel without the software-pipelined "
         "fragment reads (A/B runs)", "ops"),
+    Var("CLOUD_AMD_CONV_PATCH", bool, True, "3x3 / stride-1 / pad-1 convolutions with a 64-multiple gathered channel "
+        "count, more than 64 output columns and W <= 28 (ResNet-50 stages 2-4), forward and input gradient, on the "
+        "patch-fed core (ca_conv_patch.h: the tile's input rows go to LDS once per 64-channel chunk, not once per "
+        "tap); 0 = tap-gathered implicit GEMM (A/B runs)", "ops"),
     Var("CLOUD_AMD_CONV_EPI_PF", bool, True, "implicit-GEMM forward convolutions with the BN-statistics epilogue: "
         "read 2 staged output rows from LDS before storing", "ops"),
     Var("CLOUD_AMD_SHAPE_LOG", str, None, "profiling: append one JSON line per GEMM/convolution launch (kind, M, N, "

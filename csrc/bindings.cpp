@@ -37,6 +37,7 @@ int ca_gemm_bf16_bnstats(int, const bf16_t*, long, const bf16_t*, long, bf16_t*,
                          const bf16_t*, const uint8_t*, float*, hipStream_t);
 long ca_conv_dgrad_stat_tiles(int, int, int, int, int);
 long ca_conv_dgrad_stat_rows(int, int, int, int, int, int, int, int, int, int, int, float);
+int ca_conv_patch_shape(int, int, int, int, int, int, int, int, int, int, int, int);
 long ca_conv_stat_rows(int, int, int, int, int, int, int, int, int, int, int);
 int ca_conv_wgrad_splits(int, int, int, int, int, int, int, int, int, int, int, int);
 int ca_bn_fwd_partials_ex(const bf16_t*, const bf16_t*, const float*, bf16_t*, long, int, const float*, int,
@@ -293,6 +294,10 @@ PYBIND11_MODULE(_C, m) {
   });
   m.def("conv_stat_rows", [](int Nb, int H, int W, int Cin, int Cout, int KH, int KW, int sh, int sw, int ph,
                              int pw) { return ca_conv_stat_rows(Nb, H, W, Cin, Cout, KH, KW, sh, sw, ph, pw); });
+  m.def("conv_patch_shape", [](int Nb, int H, int W, int Cin, int Cout, int KH, int KW, int sh, int sw, int ph,
+                               int pw, int dgrad) {
+    return ca_conv_patch_shape(Nb, H, W, Cin, Cout, KH, KW, sh, sw, ph, pw, dgrad) != 0;
+  });
   m.def("conv_wgrad_splits", [](int Nb, int H, int W, int Cin, int Cout, int KH, int KW, int sh, int sw, int ph,
                                 int pw, int fallback) {
     return ca_conv_wgrad_splits(Nb, H, W, Cin, Cout, KH, KW, sh, sw, ph, pw, fallback);

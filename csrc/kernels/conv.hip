@@ -16,6 +16,7 @@
 #include <string.h>
 
 #include "ca_conv_halo.h"
+#include "ca_conv_patch.h"
 #include "ca_conv_stem.h"
 #include "ca_mfma_core.h"
 
@@ -798,6 +799,51 @@ bool tapmask_loaders() {
   return on;
 }
 
+// Stride-1 / pad-1 3x3 convolutions of ResNet stages 2-4, forward and input gradient, on the
+// patch-fed core (csrc/include/ca_conv_patch.h): the A rows of a tile go to LDS once per
+// 64-channel chunk instead of once per tap.  CLOUD_AMD_CONV_PATCH=0 keeps the tap-gathered
+// implicit GEMM (A/B runs).
+template <int PROWS, bool DGRAD, template <int, int, int> class LB, int EPI, int EPF = 1>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) conv_patch_kernel(CoreParams P) {
+  conv_patch_gemm<PROWS, DGRAD, LB, EPI, EPF>(P);
+}
+
+bool conv_patch_on() {
+  static const bool on = env_switch("CLOUD_AMD_CONV_PATCH", true);
+  return on;
+}
+
+// C: channels of the gathered tensor (Cin forward, Cout input gradient), NC: output columns.
+// (W <= 28 also keeps these apart from the width-56 halo_shape.)
+bool patch_shape(int Nb, int H, int W, int C, int NC, int KH, int KW, int sh, int sw, int ph, int pw) {
+  return conv_patch_on() && KH == 3 && KW == 3 && sh == 1 && sw == 1 && ph == 1 && pw == 1 && C % BK == 0 &&
+         NC > 64 && W <= PATCH_MAXW && use_glds() && tapmask_loaders() && (long)Nb * H * W * C * 2 < (long)BUF_CAP;
+}
+
+template <int PROWS, bool DGRAD, template <int, int, int> class LB, int EPI>
+int launch_patch_rows(const CoreParams& p, int tiles, hipStream_t s) {
+  if constexpr (EPI == EPI_BF16_ST) {
+    if (conv_epi_pf()) {
+      conv_patch_kernel<PROWS, DGRAD, LB, EPI, 2><<<dim3(tiles, 1, 1), 256, 0, s>>>(p);
+      CA_LAUNCH_CHECK();
+      return 0;
+    }
+  }
+  conv_patch_kernel<PROWS, DGRAD, LB, EPI><<<dim3(tiles, 1, 1), 256, 0, s>>>(p);
+  CA_LAUNCH_CHECK();
+  return 0;
+}
+
+template <bool DGRAD, template <int, int, int> class LB, int EPI>
+int launch_patch(const CoreParams& p0, hipStream_t s) {
+  CoreParams p = p0;
+  p.split_xcd = split_xcd_enabled();
+  const int tiles = ((p.M + 127) / 128) * ((p.N + 127) / 128);
+  // W <= 14 (stages 3-4): a 160-row patch, 36 KiB of LDS (2 % faster than the 192-row image there)
+  if (patch_rows(p.W) <= 160) return launch_patch_rows<160, DGRAD, LB, EPI>(p, tiles, s);
+  return launch_patch_rows<192, DGRAD, LB, EPI>(p, tiles, s);
+}
+
 template <int BM, int BN, template <int, int, int> class LA, template <int, int, int> class LB, int EPI>
 __global__ void __launch_bounds__(256) conv_gemm_kernel(CoreParams P) {
   mfma_gemm_body<BM, BN, 2, 2, LA, LB, EPI, 2>(P);
@@ -1000,6 +1046,8 @@ int ca_conv_fwd(const bf16_t* x, const bf16_t* w, bf16_t* y, int Nb, int H, int 
     return stats ? launch<128, 128, ConvFwdA, DenseKC, GConvRowA, GDenseKC, EPI_BF16_ST>(p, 1, s)
                  : launch<128, 128, ConvFwdA, DenseKC, GConvRowA, GDenseKC, EPI_BF16>(p, 1, s);
   }
+  if (patch_shape(Nb, H, W, Cin, Cout, KH, KW, sh, sw, ph, pw))
+    return stats ? launch_patch<false, GDenseKC, EPI_BF16_ST>(p, s) : launch_patch<false, GDenseKC, EPI_BF16>(p, s);
   if (p.cin_tile && KH * KW <= 32 && tapmask_loaders()) {
     if (stats) {
       if (Cout <= 64) return launch_n64<ConvFwdA, DenseKC, GConvFwdAT, GDenseKC, EPI_BF16_ST>(p, s);
@@ -1066,6 +1114,8 @@ long ca_conv_dgrad_stat_tiles(int Nb, int H, int W, int sh, int sw) {
 
 template <int EPI>
 static int launch_dgrad(const CoreParams& p, int Cin, hipStream_t s) {
+  if (patch_shape(p.Nb, p.H, p.W, p.Cout, Cin, p.KH, p.KW, p.sh, p.sw, p.ph, p.pw))
+    return launch_patch<true, GConvDgradBT, EPI>(p, s);
   if (p.cout_tile && p.sh == 1 && p.sw == 1 && p.KH * p.KW <= 32 && tapmask_loaders()) {
     if (Cin <= 64) return launch_n64<ConvDgradA, ConvDgradB, GConvDgradAT, GConvDgradBT, EPI>(p, s);
     return launch<128, 128, ConvDgradA, ConvDgradB, GConvDgradAT, GConvDgradBT, EPI>(p, 1, s);
@@ -1217,6 +1267,13 @@ int ca_conv_wgrad_splits(int Nb, int H, int W, int Cin, int Cout, int KH, int KW
                          int fallback) {
   if (halo_shape(H, W, Cin, Cout, KH, KW, sh, sw, ph, pw) && halo_wgrad_on()) return halo_grid(Nb, H);
   return fallback;
+}
+
+// Whether ca_conv_fwd (dgrad = 0) / ca_conv_dgrad* (dgrad = 1) run this geometry on the patch-fed core.
+int ca_conv_patch_shape(int Nb, int H, int W, int Cin, int Cout, int KH, int KW, int sh, int sw, int ph, int pw,
+                        int dgrad) {
+  return dgrad ? patch_shape(Nb, H, W, Cout, Cin, KH, KW, sh, sw, ph, pw)
+               : patch_shape(Nb, H, W, Cin, Cout, KH, KW, sh, sw, ph, pw);
 }
 
 int ca_conv_out_hw(int H, int KH, int sh, int ph) { return (H + 2 * ph - KH) / sh + 1; }
