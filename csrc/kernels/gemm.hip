@@ -519,12 +519,15 @@ int xa_dw_launch(const CoreParams& p, const XaParams& x, const bf16_t* Y, long l
   if (p.bnz2) {
     if constexpr (KS == 1) xa_dw_kernel<EPI_BF16_BNR2, KS, NC, BN, NT><<<g, NT, 0, s>>>(p, x, Y, ldy, ws, tpb);
     else return -2;
-  } else if (p.res_src) {
+  } else if (p.res_src && p.bnz) {
     if constexpr (KS == 1) xa_dw_kernel<EPI_BF16_BNR, KS, NC, BN, NT><<<g, NT, 0, s>>>(p, x, Y, ldy, ws, tpb);
     else return -2;
   } else if (p.bnz) {
     xa_dw_kernel<EPI_BF16_BN, KS, NC, BN, NT><<<g, NT, 0, s>>>(p, x, Y, ldy, ws, tpb);
   } else {
+    // also the residual-gated beta without a BN (as ca_gemm_xa): EPI_BF16 honours res_src /
+    // res_mask; EPI_BF16_BNR would read bnz and write stats, both null here
+    if (p.res_src && KS != 1) return -2;
     xa_dw_kernel<EPI_BF16, KS, NC, BN, NT><<<g, NT, 0, s>>>(p, x, Y, ldy, ws, tpb);
   }
   CA_LAUNCH_CHECK();
