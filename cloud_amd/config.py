@@ -109,7 +109,7 @@ _VARS = [
     Var("CLOUD_AMD_SMALLK_SET", str, "", "bench/smallk_gemm.py shape set ('conv3': the conv3 expansions of "
         "stages 2-4)", "bench"),
     Var("CLOUD_AMD_EPI_PF", bool, True, "GEMM epilogues that read memory or run an activation (BN-statistics "
-        "forward 1x1 convs, BERT bias/GELU/GELU'/beta dense layers): 4 staged output rows in flight per trip", "ops"),
+        "and inference-BN forward 1x1 convs, BERT bias/GELU/GELU'/beta dense layers): 4 staged output rows in flight per trip", "ops"),
     Var("CLOUD_AMD_ATTN_FUSED_BWD", bool, True, "attention at S = 64 / 128: one workgroup per (batch, head) for "
         "the forward and a single fused backward kernel; 0 keeps the 64-query-block kernels", "ops"),
     Var("CLOUD_AMD_CONV_HALO_WGRAD", bool, True, "the weight gradient of the same 3x3 / 64-channel / width-56 "
@@ -132,8 +132,12 @@ _VARS = [
         "count, more than 64 output columns and W <= 28 (ResNet-50 stages 2-4), forward and input gradient, on the "
         "patch-fed core (ca_conv_patch.h: the tile's input rows go to LDS once per 64-channel chunk, not once per "
         "tap); 0 = tap-gathered implicit GEMM (A/B runs)", "ops"),
-    Var("CLOUD_AMD_CONV_EPI_PF", bool, True, "implicit-GEMM forward convolutions with the BN-statistics epilogue: "
-        "read 2 staged output rows from LDS before storing", "ops"),
+    Var("CLOUD_AMD_CONV_EPI_PF", bool, True, "implicit-GEMM forward convolutions with the BN-statistics epilogue, and "
+        "with the inference BN + residual + ReLU epilogue: read 2 staged output rows from LDS before storing", "ops"),
+    Var("CLOUD_AMD_INFER_FUSE", bool, True, "ResNet blocks and stem that are not training (eval mode, or a frozen "
+        "Keras base) under torch.no_grad(): every BatchNorm (+ residual + ReLU) in the epilogue of its convolution "
+        "(ops.conv_bn_act_infer, ca_conv_fwd_bn) and no BN-statistics partials; 0 = the per-layer route "
+        "(convolution with statistics, then bn_apply)", "ops"),
     Var("CLOUD_AMD_SHAPE_LOG", str, None, "profiling: append one JSON line per GEMM/convolution launch (kind, M, N, "
         "K, minimum HBM bytes) to this file, for scripts/gemm_roofline.py", "ops"),
     Var("CLOUD_AMD_BN_FOLD", bool, True, "ResNet block backward: the bn3 / bn1 backward apply runs in the operand "

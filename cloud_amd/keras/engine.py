@@ -140,9 +140,23 @@ class Layer(nn.Module):
 
     @trainable.setter
     def trainable(self, v):
-        self._trainable = bool(v)
+        v = bool(v)
+        for m in self.modules():  # (self included) Keras: the flag reaches every nested layer
+            if isinstance(m, Layer):
+                m._trainable = v
         for p in self.parameters():
-            p.requires_grad_(self._trainable)
+            p.requires_grad_(v)
+
+    # Layers that run in inference mode while frozen (Keras, TF >= 2.0: a BatchNormalization
+    # with trainable = False normalises with its moving statistics and leaves them alone, in
+    # fit() too) set this; train() then keeps them in eval mode.
+    _frozen_runs_inference = False
+
+    def train(self, mode=True):
+        super().train(mode)  # children run this method themselves
+        if mode and self._frozen_runs_inference and not self._trainable:
+            super().train(False)
+        return self
 
     @property
     def weights(self):

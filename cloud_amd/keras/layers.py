@@ -274,9 +274,13 @@ class BatchNormalization(Layer):
         self.register_buffer("moving_mean", torch.zeros(c))
         self.register_buffer("moving_variance", torch.ones(c))
 
+    _frozen_runs_inference = True
+
     def call(self, x, training=None):
+        # frozen (trainable = False) means inference mode, whatever `training` says
         return ops.bn_act(x.contiguous(), self.gamma, self.beta, self.moving_mean, self.moving_variance,
-                          eps=self.epsilon, momentum=1.0 - self.momentum, relu=False, training=bool(training))
+                          eps=self.epsilon, momentum=1.0 - self.momentum, relu=False,
+                          training=bool(training) and self._trainable)
 
     def get_config(self):
         c = super().get_config()

@@ -14,6 +14,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
+from ..ops import _ext
 
 
 class Conv2d(nn.Module):
@@ -43,6 +44,32 @@ class BatchNormAct(nn.Module):
         self.bias = nn.Parameter(torch.zeros(c, device=device))
         self.register_buffer("running_mean", torch.zeros(c, device=device))
         self.register_buffer("running_var", torch.ones(c, device=device))
+
+    def folded(self):
+        """The inference form of this BatchNorm as one fp32 ``[2C]`` tensor ``[scale | shift]``:
+        ``scale = weight / sqrt(running_var + eps)``, ``shift = bias - running_mean * scale``.
+        Cached; recomputed when ``weight``, ``bias``, ``running_mean`` or ``running_var`` was written
+        in place or replaced (their ``_version`` / ``data_ptr``), so a steady-state forward only
+        compares a few integers.  The native kernels write through raw pointers, which bumps no
+        version: entering training mode drops the cache (the running statistics only move in a
+        training forward), and while weight / bias are trainable the key also carries the fused
+        optimizers' update count."""
+        srcs = (self.weight, self.bias, self.running_mean, self.running_var)
+        epoch = _ext.param_epoch[0] if (self.weight.requires_grad or self.bias.requires_grad) else -1
+        key = tuple(v for t in srcs for v in (t._version, t.data_ptr())) + (self.eps, epoch)
+        hit = self.__dict__.get("_folded")
+        if hit is not None and hit[0] == key:
+            return hit[1]
+        with torch.no_grad():
+            scale = self.weight.float() * torch.rsqrt(self.running_var.float() + self.eps)
+            ss = torch.cat([scale, self.bias.float() - self.running_mean.float() * scale]).contiguous()
+        self.__dict__["_folded"] = (key, ss)  # (not a buffer: stays out of state_dict)
+        return ss
+
+    def train(self, mode=True):
+        if mode:
+            self.__dict__.pop("_folded", None)
+        return super().train(mode)
 
     def forward(self, x, residual=None, partials=None):
         if isinstance(x, tuple):  # (conv output, fused statistics partials)

@@ -13,7 +13,7 @@ import torch
 import torch.nn as nn
 
 from . import fused_block
-from .. import config
+from .. import config, ops
 from ..ops import conv as conv_ops
 from ..ops import pooling as pool_ops
 from .layers import BatchNormAct, Conv2d, GlobalAvgPool, Linear, MaxPool2d
@@ -40,7 +40,34 @@ class Bottleneck(nn.Module):
                 "bn": BatchNormAct(cout, relu=False, device=device),
             })
 
+    def infer_fusable(self, x):
+        """The block runs as conv + BN (+ residual) + ReLU launches (ops.conv_bn_act_infer): it is
+        not training (eval mode, or frozen by the Keras layer), nothing needs a gradient, and
+        CLOUD_AMD_INFER_FUSE is on.  CPU / fp32 / ``CLOUD_AMD_OPS=torch`` tensors take the
+        same route through the op's torch formula."""
+        return (not self.training and not torch.is_grad_enabled() and not x.requires_grad
+                and config.get("CLOUD_AMD_INFER_FUSE") and x.is_contiguous())
+
+    def forward_infer(self, x):
+        """Four launches (three without a projection): every BatchNorm in its convolution's epilogue,
+        the shortcut as conv3's residual operand."""
+        def cba(conv, bn, t, residual=None):
+            ss = bn.folded()
+            c = bn.c
+            return ops.conv_bn_act_infer(t, conv.weight.detach(), ss[:c], ss[c:], stride=conv.stride,
+                                         padding=conv.padding, residual=residual, relu=bn.relu)
+
+        identity = x
+        if self.downsample is not None:
+            identity = cba(self.downsample["conv"], self.downsample["bn"], x)
+        out = cba(self.conv1, self.bn1, x)
+        out = cba(self.conv2, self.bn2, out)
+        return cba(self.conv3, self.bn3, out, residual=identity)
+
     def forward(self, x, next_block=None):
+        if self.infer_fusable(x):
+            fused_block.check_not_pending(x)
+            return self.forward_infer(x)
         if self.fused_block and fused_block.can_fuse(self, x):
             return fused_block.bottleneck_forward(self, x, next_block)
         fused_block.check_not_pending(x)
@@ -77,15 +104,7 @@ class ResNet(nn.Module):
 
     def forward(self, x):
         """x: NHWC [N, H, W, in_channels] in the compute dtype -> logits [N, classes]."""
-        c1 = self.conv1
-        if self.stem_s2d and x.shape[-1] == self.in_channels and conv_ops.stem_s2d_ok(x, c1.weight, c1.stride,
-                                                                                         c1.padding):
-            # 7x7/2 stem as a 4x4/1 conv over the space-to-depth input (no channel pad pass)
-            x = self._stem_tail(conv_ops.stem_conv_s2d(x, c1.weight, stats=True))
-        else:
-            if self.stem_cin != self.in_channels:
-                x = torch.nn.functional.pad(x, (0, self.stem_cin - self.in_channels))
-            x = self._stem_tail(self.conv1(x, stats=True))
+        x = self.stem(x)
         if self.layers._forward_hooks or self.layers._forward_pre_hooks:
             # hooks on the block Sequential: call it (they fire; no cross-block BN fold)
             x = self.layers(x)
@@ -96,10 +115,27 @@ class ResNet(nn.Module):
                 x = blk(x, blocks[i + 1] if i + 1 < len(blocks) else None)
         return self.fc(self.pool(x))
 
-    def _stem_tail(self, out):
+    def stem(self, x):
+        """maxpool(bn1(conv1(x))) for x [N, H, W, in_channels]."""
+        c1 = self.conv1
+        # inference (eval mode or frozen): the convolution without BN-statistics partials
+        infer = (not self.bn1.training and not torch.is_grad_enabled() and not x.requires_grad
+                 and config.get("CLOUD_AMD_INFER_FUSE"))
+        if self.stem_s2d and x.shape[-1] == self.in_channels and conv_ops.stem_s2d_ok(x, c1.weight, c1.stride,
+                                                                                         c1.padding):
+            # 7x7/2 stem as a 4x4/1 conv over the space-to-depth input (no channel pad pass)
+            return self._stem_tail(conv_ops.stem_conv_s2d(x, c1.weight, stats=not infer), infer)
+        if self.stem_cin != self.in_channels:
+            x = torch.nn.functional.pad(x, (0, self.stem_cin - self.in_channels))
+        return self._stem_tail(self.conv1(x, stats=not infer), infer)
+
+    def _stem_tail(self, out, infer=False):
         """maxpool(bn1(conv1 output)): in training, BN + ReLU + max-pool fused into one pass
         each way (the 112x112x64 BN output is never materialised); else the separate ops."""
         z, part = out if isinstance(out, tuple) else (out, None)
+        if infer and pool_ops.stem_infer_ok(z, self.bn1, self.maxpool):
+            # BN (running statistics) + ReLU + max-pool in one pass, as the training step's tail
+            return pool_ops.stem_bn_relu_maxpool_infer(z, self.bn1)
         if config.get("CLOUD_AMD_STEM_TAIL") and pool_ops.stem_tail_ok(z, self.bn1, self.maxpool, part):
             return pool_ops.stem_bn_relu_maxpool(z, self.bn1, part)
         return self.maxpool(self.bn1((z, part) if part is not None else z))

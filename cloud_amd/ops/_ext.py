@@ -60,6 +60,11 @@ def use_native(*tensors) -> bool:
     return True
 
 
+# Counts optimizer updates that write parameters through raw device pointers: such a write
+# bumps no tensor ``_version``, so caches derived from TRAINABLE parameters (BatchNormAct.folded)
+# key on this counter as well.
+param_epoch = [0]
+
 _RAW_STREAM = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 
 

@@ -181,3 +181,24 @@ def stem_tail_ok(z, bn, pool, partials):
 def stem_bn_relu_maxpool(z, bn, partials):
     """The ResNet stem tail ``maxpool(bn1(z))`` of a training step, fused (see _StemTailFn)."""
     return _StemTailFn.apply(z, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, bn.momentum, partials)
+
+
+def stem_infer_ok(z, bn, pool):
+    """The fused stem tail applies to an inference forward (no statistics, no backward)."""
+    return (bn.relu and z.is_cuda and z.dtype == torch.bfloat16 and z.is_contiguous() and z.shape[-1] % 8 == 0
+            and z.shape[0] * z.shape[1] * z.shape[2] < 2 ** 31 and not z.requires_grad
+            and (pool.k, pool.stride, pool.padding) == (3, 2, 1) and _ext.use_native(z))
+
+
+def stem_bn_relu_maxpool_infer(z, bn):
+    """``maxpool(relu(bn(z)))`` of the ResNet stem with the BatchNorm in inference form: the
+    same ``bn_relu_maxpool_s2k3`` pass as the training step, fed the folded running statistics
+    (``bn.folded()``).  The argmax bytes it also writes feed a backward that never runs here."""
+    ext = _ext.load(required=True)
+    N, H, W, C = z.shape
+    OH, OW = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    y = torch.empty((N, OH, OW, C), dtype=torch.bfloat16, device=z.device)
+    idx = torch.empty((N, OH, OW, C), dtype=torch.uint8, device=z.device)  # scratch
+    ext.bn_relu_maxpool_s2k3(z.data_ptr(), bn.folded().data_ptr(), y.data_ptr(), idx.data_ptr(), N, H, W, C, OH, OW,
+                             _ext.stream_handle(z.device))
+    return y

@@ -106,6 +106,27 @@ def conv_fwd(x, w, stride, padding, stats=None):
     return y
 
 
+def conv_fwd_bn(x, w, scale, shift, stride, padding, residual=None, relu=True, out=None):
+    """y = act(conv(x, w) * scale[c] + shift[c] (+ residual)) in one launch (inference BatchNorm in the
+    convolution epilogue); scale / shift fp32 [Cout], residual bf16 of y's shape or None."""
+    ext = _ext.load(required=True)
+    N, H, W, Cin = x.shape
+    Cout, KH, KW, _ = w.shape
+    OH, OW = out_hw(H, KH, stride, padding), out_hw(W, KW, stride, padding)
+    assert x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and x.is_contiguous() and w.is_contiguous()
+    assert scale.dtype == torch.float32 and shift.dtype == torch.float32 and scale.numel() == Cout == shift.numel()
+    assert scale.is_contiguous() and shift.is_contiguous()
+    if residual is not None:
+        assert residual.dtype == torch.bfloat16 and tuple(residual.shape) == (N, OH, OW, Cout)
+        residual = residual.contiguous()
+    y = out if out is not None else torch.empty((N, OH, OW, Cout), dtype=torch.bfloat16, device=x.device)
+    assert tuple(y.shape) == (N, OH, OW, Cout) and y.is_contiguous() and y.dtype == torch.bfloat16
+    ext.conv_fwd_bn(x.data_ptr(), w.data_ptr(), y.data_ptr(), N, H, W, Cin, Cout, KH, KW, stride, stride, padding,
+                    padding, scale.data_ptr(), shift.data_ptr(), _ext.ptr(residual), 2 if relu else 0, _st(x.device))
+    _log("fwdbn%dx%ds%d" % (KH, KW, stride), N * OH * OW, Cout, KH * KW * Cin, _nb(x, w, y, residual))
+    return y
+
+
 def conv_dgrad(dy, w, x_shape, stride, padding, out=None, beta=0.0, bn=None, res=None, beta_stride=1,
                skip_empty=False):
     """dx (+= beta * out) for y = conv(x, w).

@@ -210,6 +210,7 @@ class FusedOptimizer:
         return self.fuse_zero_grad and self._use_native(a)
 
     def _after_update(self):
+        _ext.param_epoch[0] += 1  # parameters written through raw pointers (no tensor version bump)
         self._grads_clean = bool(self.arenas) and all(self._zero_in_kernel(a) for a in self.arenas)
 
     def _clip(self):

@@ -85,6 +85,8 @@ int ca_conv_fwd_ex(const bf16_t*, const bf16_t*, bf16_t*, int, int, int, int, in
                    const float*, int, hipStream_t);
 int ca_conv_fwd(const bf16_t*, const bf16_t*, bf16_t*, int, int, int, int, int, int, int, int, int, int, int, float*,
                 hipStream_t);
+int ca_conv_fwd_bn(const bf16_t*, const bf16_t*, bf16_t*, int, int, int, int, int, int, int, int, int, int, int,
+                   const float*, const float*, const bf16_t*, int, hipStream_t);
 int ca_conv_dgrad(const bf16_t*, const bf16_t*, bf16_t*, int, int, int, int, int, int, int, int, int, int, int, float,
                   hipStream_t, int);
 int ca_conv_wgrad(const bf16_t*, const bf16_t*, void*, int, float, int, int, int, int, int, int, int, int, int, int,
@@ -349,6 +351,12 @@ PYBIND11_MODULE(_C, m) {
                        int ph, int pw, u64 stats, u64 s) {
     check(ca_conv_fwd(P(const bf16_t*, x), P(const bf16_t*, w), P(bf16_t*, y), Nb, H, W, Cin, Cout, KH, KW, sh, sw, ph,
                       pw, P(float*, stats), S(s)), "conv_fwd");
+  });
+  m.def("conv_fwd_bn", [](u64 x, u64 w, u64 y, int Nb, int H, int W, int Cin, int Cout, int KH, int KW, int sh,
+                          int sw, int ph, int pw, u64 scale, u64 shift, u64 residual, int act, u64 s) {
+    check(ca_conv_fwd_bn(P(const bf16_t*, x), P(const bf16_t*, w), P(bf16_t*, y), Nb, H, W, Cin, Cout, KH, KW, sh, sw,
+                         ph, pw, P(const float*, scale), P(const float*, shift), P(const bf16_t*, residual), act,
+                         S(s)), "conv_fwd_bn");
   });
   m.def("bn_relu_maxpool_s2k3", [](u64 z, u64 ss, u64 y, u64 idx, int N, int H, int W, int C, int OH, int OW,
                                    u64 s) {

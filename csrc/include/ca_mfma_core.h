@@ -49,7 +49,14 @@ __device__ __forceinline__ uint32_t buf_span(long bytes) {
 // EPI_BF16_BNR2: EPI_BF16_BNR that also sums g * z2 for a second BatchNorm fed by the same
 // gradient (CoreParams::bnz2 / stats2: the projection shortcut's BN, whose input is the
 // shortcut convolution output and whose output gradient is the same gated block gradient).
-enum Epi { EPI_BF16 = 0, EPI_F32_PARTIAL = 1, EPI_BF16_BN = 2, EPI_BF16_ST = 3, EPI_BF16_BNR = 4, EPI_BF16_BNR2 = 5 };
+// EPI_BF16_AFF: inference epilogue of a convolution followed by a frozen BatchNorm:
+// C = act(acc * scale[col] + bias[col] (+ res_src)), the affine in fp32 on the accumulators, the
+// residual add and the activation (ACT_NONE / ACT_RELU, AFTER the add) in the row pass.  None of
+// the dense-layer / beta / statistics options apply to it.
+enum Epi {
+  EPI_BF16 = 0, EPI_F32_PARTIAL = 1, EPI_BF16_BN = 2, EPI_BF16_ST = 3, EPI_BF16_BNR = 4, EPI_BF16_BNR2 = 5,
+  EPI_BF16_AFF = 6
+};
 
 // Fast unsigned division by a runtime constant (n < 2^31): q = (umulhi(n, m) + n) >> s.
 struct FastDiv {
@@ -114,6 +121,7 @@ struct CoreParams {
   // convolution's input gradient, written for its one non-empty parity class only)
   int bpar_s;
   FastDiv div_bpw, div_bph;
+  const float* scale;  // EPI_BF16_AFF: per-column fp32 multiplier [N] (bias carries the shift)
 };
 
 // whether the beta-accumulate source of output row `orow` is stored (see CoreParams::bpar_s)
@@ -462,7 +470,19 @@ __device__ __forceinline__ void gemm_epilogue(const CoreParams& P, f4v (&acc)[FM
     return;
   } else {
     short* Cs = smem;
-    if (!BIAS_IN_ACC && P.bias) {  // (BIAS_IN_ACC: the core started its accumulators at the bias)
+    if constexpr (EPI == EPI_BF16_AFF) {  // BN affine: one fp32 FMA per accumulator
+#pragma unroll
+      for (int j = 0; j < FN; ++j) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int gn = n0 + fcol(j) + r;
+          const int cn = gn < P.N ? gn : P.N - 1;
+          const float sc = P.scale[cn], sf = P.bias[cn];
+#pragma unroll
+          for (int i = 0; i < FM; ++i) acc[i][j][r] = bn_affine(acc[i][j][r], sc, sf);
+        }
+      }
+    } else if (!BIAS_IN_ACC && P.bias) {  // (BIAS_IN_ACC: the core started its accumulators at the bias)
 #pragma unroll
       for (int j = 0; j < FN; ++j) {
 #pragma unroll
@@ -484,6 +504,45 @@ __device__ __forceinline__ void gemm_epilogue(const CoreParams& P, f4v (&acc)[FM
         *reinterpret_cast<s4v*>(Cs + EL::idx(frow(i), fcol(j))) = pk;
       }
     __syncthreads();
+    if constexpr (EPI == EPI_BF16_AFF) {
+      // row pass of the affine epilogue: residual (8 channels per thread, PF rows' loads in
+      // flight per trip) added to the staged bf16 value, then the ReLU
+      constexpr int AIT = BM * BN / 8 / NT;
+      constexpr int APF = AIT < EPF ? AIT : EPF;
+      static_assert((BM * BN / 8) % NT == 0 && NT % (BN / 8) == 0, "affine epilogue: fixed column group per thread");
+      bf16_t* Cg = reinterpret_cast<bf16_t*>(P.C);
+      const int gn = n0 + (tid % (BN / 8)) * 8;
+      const int row0 = tid / (BN / 8);
+      const bool relu = P.act == ACT_RELU;
+      if (gn >= P.N) return;  // (no barrier follows)
+#pragma unroll 1
+      for (int it0 = 0; it0 < AIT; it0 += APF) {
+        s8v rpre[APF];
+#pragma unroll
+        for (int u = 0; u < APF; ++u) {
+          const int gm = m0 + row0 + (it0 + u) * (NT / (BN / 8));
+          rpre[u] = (P.res_src && gm < P.M) ? *reinterpret_cast<const s8v*>(P.res_src + (long)gm * P.ldc + gn)
+                                            : zero8();
+        }
+#pragma unroll
+        for (int u = 0; u < APF; ++u) {
+          const int row = row0 + (it0 + u) * (NT / (BN / 8));
+          const int gm = m0 + row;
+          if (gm >= P.M) continue;
+          s8v v = *reinterpret_cast<const s8v*>(Cs + EL::idx(row, gn - n0));
+          if (P.res_src) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = (short)f2bf(bf2f((bf16_t)v[j]) + bf2f((bf16_t)rpre[u][j]));
+          }
+          if (relu) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = v[j] > 0 ? v[j] : (short)0;  // on the bf16 bits: sign set or zero -> +0
+          }
+          *reinterpret_cast<s8v*>(Cg + (long)gm * P.ldc + gn) = v;
+        }
+      }
+      return;
+    }
     const bool fx = P.act != ACT_NONE || P.dact_src != nullptr || P.preact != nullptr;
     bf16_t* Cg = reinterpret_cast<bf16_t*>(P.C);
     float bsum[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, bzsum[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};

@@ -822,7 +822,7 @@ bool patch_shape(int Nb, int H, int W, int C, int NC, int KH, int KW, int sh, in
 
 template <int PROWS, bool DGRAD, template <int, int, int> class LB, int EPI>
 int launch_patch_rows(const CoreParams& p, int tiles, hipStream_t s) {
-  if constexpr (EPI == EPI_BF16_ST) {
+  if constexpr (EPI == EPI_BF16_ST || EPI == EPI_BF16_AFF) {
     if (conv_epi_pf()) {
       conv_patch_kernel<PROWS, DGRAD, LB, EPI, 2><<<dim3(tiles, 1, 1), 256, 0, s>>>(p);
       CA_LAUNCH_CHECK();
@@ -855,7 +855,7 @@ int launch(const CoreParams& p0, int splits, hipStream_t s) {
   CoreParams p = p0;
   p.split_xcd = split_xcd_enabled();
   const int tiles = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
-  if constexpr (EPI == EPI_BF16_ST) {
+  if constexpr (EPI == EPI_BF16_ST || EPI == EPI_BF16_AFF) {
     if (use_glds() && conv_epi_pf()) {
       conv_glds_kernel<BM, BN, GA, GB, EPI, 2><<<dim3(tiles, 1, splits), 256, 0, s>>>(p);
       CA_LAUNCH_CHECK();
@@ -880,7 +880,7 @@ int launch_n64(const CoreParams& p0, hipStream_t s) {
   CoreParams p = p0;
   p.split_xcd = split_xcd_enabled();
   const int tiles = (p.M + 255) / 256;
-  if constexpr (EPI == EPI_BF16_ST) {
+  if constexpr (EPI == EPI_BF16_ST || EPI == EPI_BF16_AFF) {
     if (conv_epi_pf()) {
       conv_glds_w_kernel<256, 64, 4, 1, GA, GB, EPI, 2><<<dim3(tiles, 1, 1), 256, 0, s>>>(p);
       CA_LAUNCH_CHECK();
@@ -1076,6 +1076,47 @@ int ca_conv_fwd_ex(const bf16_t* x, const bf16_t* w, bf16_t* y, int Nb, int H, i
   p.act = act;
   if (Cout <= 64) return launch<128, 64, ConvFwdA, DenseKC, GConvFwdA, GDenseKC, EPI_BF16>(p, 1, s);
   return launch<128, 128, ConvFwdA, DenseKC, GConvFwdA, GDenseKC, EPI_BF16>(p, 1, s);
+}
+
+int ca_gemm_bn(const bf16_t*, long, const bf16_t*, long, bf16_t*, long, int, int, int, const float*, const float*,
+               const bf16_t*, int, hipStream_t);
+
+// Inference form of convolution + frozen BatchNorm (+ residual) (+ ReLU) in one launch:
+//   y = act(conv(x, w) * scale[c] + shift[c] (+ residual)),  act = ACT_NONE or ACT_RELU,
+// scale / shift fp32 [Cout], residual bf16 NHWC of y's shape or null (EPI_BF16_AFF).  The
+// dispatch is ca_conv_fwd's, except that the LDS-resident halo and stem kernels
+// (ca_conv_halo.h, ca_conv_stem.h) are not used -- they have epilogues of their own; their
+// shapes run on the implicit-GEMM kernels here (tall tap-mask tiles / row-segment loader) --
+// and a 1x1 / stride-1 / pad-0 convolution is the dense NT GEMM of gemm.hip on its 128 core
+// (not the resident-weight or 256 x 256 cores, for the same reason).
+int ca_conv_fwd_bn(const bf16_t* x, const bf16_t* w, bf16_t* y, int Nb, int H, int W, int Cin, int Cout, int KH,
+                   int KW, int sh, int sw, int ph, int pw, const float* scale, const float* shift,
+                   const bf16_t* residual, int act, hipStream_t s) {
+  CoreParams p = conv_params(Nb, H, W, Cin, Cout, KH, KW, sh, sw, ph, pw);
+  if (!geom_ok(Cin, Cout, (long)Nb * H * W) || !scale || !shift || (act != ACT_NONE && act != ACT_RELU)) return -1;
+  if (p.OH <= 0 || p.OW <= 0) return -1;
+  if (KH == 1 && KW == 1 && sh == 1 && sw == 1 && ph == 0 && pw == 0)
+    return ca_gemm_bn(x, Cin, w, Cin, y, Cout, Nb * H * W, Cout, Cin, scale, shift, residual, act, s);
+  p.A = x; p.B = w; p.lda = Cin; p.ldb = (long)KH * KW * Cin; p.C = y; p.ldc = Cout;
+  p.M = Nb * p.OH * p.OW; p.N = Cout; p.K = KH * KW * Cin; p.k_per_split = p.K;
+  p.scale = scale;
+  p.bias = shift;
+  p.res_src = residual;
+  p.act = act;
+  constexpr int E = EPI_BF16_AFF;
+  if (sh == 1 && sw == 1 && ph == 0 && pw == 0 && KW * Cin == BK && tapmask_loaders() && use_glds() &&
+      (long)Nb * H * W * Cin * 2 < (long)BUF_CAP) {
+    if (Cout <= 64 && stem_tall()) return launch_n64<ConvFwdA, DenseKC, GConvRowA, GDenseKC, E>(p, s);
+    if (Cout <= 64) return launch<128, 64, ConvFwdA, DenseKC, GConvRowA, GDenseKC, E>(p, 1, s);
+    return launch<128, 128, ConvFwdA, DenseKC, GConvRowA, GDenseKC, E>(p, 1, s);
+  }
+  if (patch_shape(Nb, H, W, Cin, Cout, KH, KW, sh, sw, ph, pw)) return launch_patch<false, GDenseKC, E>(p, s);
+  if (p.cin_tile && KH * KW <= 32 && tapmask_loaders()) {
+    if (Cout <= 64) return launch_n64<ConvFwdA, DenseKC, GConvFwdAT, GDenseKC, E>(p, s);
+    return launch<128, 128, ConvFwdA, DenseKC, GConvFwdAT, GDenseKC, E>(p, 1, s);
+  }
+  if (Cout <= 64) return launch<128, 64, ConvFwdA, DenseKC, GConvFwdA, GDenseKC, E>(p, 1, s);
+  return launch<128, 128, ConvFwdA, DenseKC, GConvFwdA, GDenseKC, E>(p, 1, s);
 }
 
 // Rows of the BN-backward statistics partials ca_conv_dgrad_bnstats writes: one per

@@ -378,7 +378,7 @@ int launch(const CoreParams& p0, int splits, hipStream_t s) {
   // activation: 4 rows' loads in flight per trip instead of one (BERT FFN2 dgrad with
   // GELU': one HBM round trip per staged row otherwise)
   constexpr bool PLAIN = EPI == EPI_BF16;
-  if constexpr (PLAIN || (EPI == EPI_BF16_ST && GA<BM, 1, 256>::KC && GB<BN, 1, 256>::KC)) {
+  if constexpr (PLAIN || ((EPI == EPI_BF16_ST || EPI == EPI_BF16_AFF) && GA<BM, 1, 256>::KC && GB<BN, 1, 256>::KC)) {
     const bool want = !PLAIN || p.dact_src || p.act || p.beta != 0.f;
     if (want && use_glds() && epi_pf()) {
       dense_gemm_glds_pf_kernel<BM, BN, GA, GB, EPI><<<dim3(tiles, 1, splits), 256, 0, s>>>(p);
@@ -732,6 +732,22 @@ int ca_dgrad_gemm(int layout, const bf16_t* A, long lda, const bf16_t* B, long l
                               : launch<128, 128, DenseKC, DenseNC, GDenseKC, GDenseNC, EPI_BF16_BNR>(p, 1, s);
   return want_small_n(p, 1) ? launch<128, 64, DenseKC, DenseNC, GDenseKC, GDenseNC, EPI_BF16_BN>(p, 1, s)
                             : launch<128, 128, DenseKC, DenseNC, GDenseKC, GDenseNC, EPI_BF16_BN>(p, 1, s);
+}
+
+// Forward 1x1 convolution + frozen BatchNorm (+ residual) (+ ReLU), NT layout:
+// C = act((A * B^T) * scale[n] + shift[n] (+ residual)) with residual [M][ldc] bf16 or null
+// (EPI_BF16_AFF), on the 128 core with the tile width of dispatch<>.
+int ca_gemm_bn(const bf16_t* A, long lda, const bf16_t* B, long ldb, bf16_t* C, long ldc, int M, int N, int K,
+               const float* scale, const float* shift, const bf16_t* residual, int act, hipStream_t s) {
+  if (M <= 0 || N < 8 || N % 8 != 0 || K % 8 != 0 || !scale || !shift) return -1;
+  if (act != ACT_NONE && act != ACT_RELU) return -1;
+  CoreParams p = base_params(A, lda, B, ldb, C, ldc, M, N, K);
+  p.scale = scale;
+  p.bias = shift;
+  p.res_src = residual;
+  p.act = act;
+  return want_small_n(p, 1) ? launch<128, 64, DenseKC, DenseKC, GDenseKC, GDenseKC, EPI_BF16_AFF>(p, 1, s)
+                            : launch<128, 128, DenseKC, DenseKC, GDenseKC, GDenseKC, EPI_BF16_AFF>(p, 1, s);
 }
 
 // Dense-layer GEMM with the fused epilogue: C = act(A*B + bias) (+ beta*C),
