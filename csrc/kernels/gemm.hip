@@ -659,15 +659,18 @@ int ca_splitk_reduce(const float* ws, int splits, long MN, void* out, int out_bf
 }
 
 // C = A*B (+ beta*C) in bf16.  stats != null -> per-128-row-tile column [sum|sumsq] partials.
+// The persistent resident-weight core has no beta term (it does not go through gemm_epilogue),
+// so it is taken for beta == 0 only; with a beta the tiled core runs, also with statistics.
 int ca_gemm_bf16(int layout, const bf16_t* A, long lda, const bf16_t* B, long ldb, bf16_t* C, long ldc,
                  int M, int N, int K, float* stats, float beta, hipStream_t s) {
   if (M <= 0 || N < 8 || N % 8 != 0 || K % 8 != 0 || (layout == 2 && M % 8 != 0)) return -1;
   CoreParams p = base_params(A, lda, B, ldb, C, ldc, M, N, K);
   p.stats = stats;
   p.beta = beta;
-  if (!stats && layout == 0 && prw_kind(M, N, K, lda, ldb, ldc, false) == 2) return prw_launch(2, p, s);
+  const bool prw_ok = beta == 0.f;
+  if (!stats && layout == 0 && prw_ok && prw_kind(M, N, K, lda, ldb, ldc, false) == 2) return prw_launch(2, p, s);
   if (stats && layout == 0) {  // forward 1x1 conv feeding a BatchNorm: register-accumulated statistics
-    const int kind = prw_kind(M, N, K, lda, ldb, ldc, true);
+    const int kind = prw_ok ? prw_kind(M, N, K, lda, ldb, ldc, true) : 0;
     if (kind && prw_grid(kind, M) > 0) return prw_launch(kind, p, s);  // one partial row per workgroup / range
     return want_small_n(p, 1) ? launch<128, 64, DenseKC, DenseKC, GDenseKC, GDenseKC, EPI_BF16_ST>(p, 1, s)
                               : launch<128, 128, DenseKC, DenseKC, GDenseKC, GDenseKC, EPI_BF16_ST>(p, 1, s);
@@ -676,7 +679,9 @@ int ca_gemm_bf16(int layout, const bf16_t* A, long lda, const bf16_t* B, long ld
 }
 
 // Rows of the [rows][2][N] statistics partials ca_gemm_bf16(layout 0, stats != null) writes:
-// one per workgroup on the persistent core, one per 128 GEMM rows otherwise.
+// one per workgroup on the persistent core, one per 128 GEMM rows otherwise.  The answer is for
+// beta == 0, which is what every caller of this function passes to ca_gemm_bf16; a call with
+// beta != 0 stays off the persistent core and writes (M + 127) / 128 rows.
 int ca_gemm_stat_rows(int M, int N, int K, long lda, long ldb, long ldc) {
   const int kind = prw_kind(M, N, K, lda, ldb, ldc, true);
   return (kind && prw_grid(kind, M) > 0) ? prw_stat_rows(kind, M) : (M + 127) / 128;
@@ -922,6 +927,10 @@ int ca_gemm_splitk_effective(int K, int splits) {
 int ca_gemm_splitk(int layout, const bf16_t* A, long lda, const bf16_t* B, long ldb, void* out, int out_bf16,
                    float beta, int M, int N, int K, int splits, float* ws, hipStream_t s) {
   if (M <= 0 || N < 8 || N % 8 != 0 || (layout == 2 && M % 8 != 0)) return -1;
+  // K-contiguous operands (A of layouts 0 / 1, B of layout 0) are fetched in 16-byte chunks that
+  // test only their first element against K: a row's last chunk must not reach into the next row.
+  // (Layout 2 reduces over rows: any K is legal there.)
+  if (layout != 2 && K % 8 != 0) return -1;
   int kps = (K / splits + BK - 1) / BK * BK;
   if (kps < BK) kps = BK;
   splits = (K + kps - 1) / kps;
