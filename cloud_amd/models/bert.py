@@ -337,9 +337,13 @@ class BertForSequenceClassification(nn.Module):
 
     # ------------------------------------------------------------------ paths
     def _native_ok(self, input_ids):
+        # No condition on the sequence length or on the row count B * S: attention takes any S
+        # (attn.hip), the NT / NN GEMMs any M, the TN weight gradient any reduction length
+        # (gemm.hip), and the embedding, LayerNorm, column-sum, gradient-finalisation and head
+        # kernels are row-generic (rowops.hip, gradfin.hip, head.hip).
         cfg = self.cfg
         return (input_ids.is_cuda and self.dtype == torch.bfloat16 and _ext.use_native(input_ids)
-                and cfg.hidden_size // cfg.num_attention_heads == 64 and input_ids.shape[1] % 64 == 0
+                and cfg.hidden_size // cfg.num_attention_heads == 64
                 and cfg.hidden_size % 8 == 0 and cfg.intermediate_size % 8 == 0)
 
     def forward(self, input_ids, token_type_ids=None, attention_mask=None):

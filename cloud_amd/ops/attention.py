@@ -1,0 +1,84 @@
+"""Fused multi-head self-attention (K13) over a packed QKV projection.
+
+``attention(qkv, num_heads, key_len)`` computes, per batch entry and head,
+``softmax(Q K^T * scale + key mask) (dropout) V`` for ``qkv: [B, S, 3*H*D]`` packed
+``Q | K | V`` with head ``h`` at columns ``h*D`` of each third -- the layout the QKV
+projection produces and the kernels of ``csrc/kernels/attn.hip`` read in place.  The
+result is ``[B, S, H*D]``.
+
+On MI355X (contiguous bf16 CUDA tensors, ``D == 64``) forward and backward run on the
+gfx950 MFMA kernels at any sequence length (S = 64 / 128 on the one-workgroup kernels);
+the backward recomputes the probabilities from the saved log-sum-exp and regenerates the
+dropout mask from the saved seed.  CPU tensors, other dtypes and other head dimensions run
+the same math in fp32 PyTorch.
+"""
+from __future__ import annotations
+
+import math
+
+import torch
+import torch.nn.functional as F
+
+from . import _ext, raw
+from .dropout import next_seed
+
+
+class _AttentionFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, qkv, key_len, H, scale, p, seed):
+        B, S, _ = qkv.shape
+        q2 = qkv.view(B * S, -1)
+        out, lse = raw.attn_fwd(q2, B, S, H, key_len, p, seed, scale=scale)
+        ctx.save_for_backward(q2, out, lse, key_len)
+        ctx.cfg = (B, S, H, scale, p, seed)
+        return out.view(B, S, -1)
+
+    @staticmethod
+    def backward(ctx, dout):
+        q2, out, lse, key_len = ctx.saved_tensors
+        B, S, H, scale, p, seed = ctx.cfg
+        dout = dout.contiguous().view(B * S, -1)
+        dqkv = raw.attn_bwd(q2, out, dout, lse, B, S, H, key_len, p, seed, scale=scale)
+        return dqkv.view(B, S, -1), None, None, None, None, None
+
+
+def _reference(qkv, H, key_len, scale, p):
+    B, S, C3 = qkv.shape
+    D = C3 // (3 * H)
+    ct = torch.float64 if qkv.dtype == torch.float64 else torch.float32
+    q, k, v = qkv.to(ct).reshape(B, S, 3, H, D).permute(2, 0, 3, 1, 4)
+    att = (q @ k.transpose(-1, -2)) * scale
+    if key_len is not None:
+        kl = key_len.to(device=qkv.device, dtype=torch.long).clamp(1, S)
+        pad = torch.arange(S, device=qkv.device)[None, :] >= kl[:, None]
+        att = att.masked_fill(pad[:, None, None, :], float("-inf"))
+    att = att.softmax(-1)
+    if p > 0:
+        att = F.dropout(att, p, training=True)
+    return (att @ v).permute(0, 2, 1, 3).reshape(B, S, H * D).to(qkv.dtype)
+
+
+def attention(qkv, num_heads, key_len=None, dropout_p=0.0, training=True, scale=None, seed=None):
+    """Multi-head self-attention of a packed projection ``qkv [B, S, 3*H*D]`` -> ``[B, S, H*D]``.
+
+    ``key_len``: int tensor ``[B]``, the number of valid (leading) keys of each batch entry,
+    clamped to ``[1, S]``; ``None`` = all keys.  ``scale`` defaults to ``1 / sqrt(D)``.
+    Dropout acts on the attention probabilities, only when ``training``; ``seed`` (an int)
+    fixes the mask of the native path and defaults to ``ops.dropout.next_seed()``.
+
+    The two paths draw different dropout masks: the HIP kernels hash ``(seed, element
+    index)`` (``raw.dropout_mask`` reproduces it), the PyTorch reference uses ``F.dropout``
+    and the torch generator, and ignores ``seed``.
+    """
+    if qkv.dim() != 3 or qkv.shape[2] % (3 * num_heads):
+        raise ValueError(f"attention: qkv must be [B, S, 3*H*D] with H = {num_heads}, got {tuple(qkv.shape)}")
+    D = qkv.shape[2] // (3 * num_heads)
+    scale = 1.0 / math.sqrt(D) if scale is None else float(scale)
+    p = float(dropout_p) if training else 0.0
+    if (qkv.dtype == torch.bfloat16 and D == 64 and qkv.shape[0] > 0 and qkv.shape[1] > 0 and qkv.is_contiguous()
+            and _ext.use_native(qkv)):
+        kl = None if key_len is None else key_len.to(device=qkv.device, dtype=torch.int32).contiguous()
+        if p > 0 and seed is None:
+            seed = next_seed()
+        return _AttentionFn.apply(qkv, kl, num_heads, scale, p, int(seed) if p > 0 else 0)
+    return _reference(qkv, num_heads, key_len, scale, p)

@@ -888,7 +888,8 @@ def embed_bwd(dh, ids, tts, dword, dpos, dtype_, seq_len, n_types, pos_offset=0,
 
 
 def attn_fwd(qkv, B, S, H, key_len=None, p_drop=0.0, seed=0, scale=None):
-    """qkv [B*S, 3*H*64] -> (ctx [B*S, H*64], lse [B, H, S])."""
+    """qkv [B*S, 3*H*64] -> (ctx [B*S, H*64], lse [B, H, S]).  Any S; S = 64 / 128 take the
+    one-workgroup kernels."""
     ext = _ext.load(required=True)
     C = H * 64
     ctx = torch.empty((B * S, C), dtype=torch.bfloat16, device=qkv.device)

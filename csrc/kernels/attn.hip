@@ -18,6 +18,12 @@
 //   dQ   : per 64-query block, loop over key blocks: dQ += dS K
 // MFMA: v_mfma_f32_16x16x32_bf16; K-contiguous operands via ds_read_b128,
 // N-contiguous ones (V / dO / Q / K as B with k along rows) via ds_read_b64_tr_b16.
+//
+// Shapes: any S; S = 64 / 128 take the one-workgroup kernels (below), every other S the
+// generic ones on ceil(S / 64) blocks.  S % 64 != 0 runs their TAIL instantiation, which only
+// masks: fragment rows >= S are clamped to row S - 1, tile rows >= S are zero-filled in LDS,
+// lse / Dv of queries >= S are not read (dKV: p = dS = 0 for those columns), and only rows
+// < S are stored.  The non-tail instantiation is the code that ran before the split.
 #include "ca_mfma_core.h"
 #include "ca_rng.h"
 
@@ -31,14 +37,34 @@ constexpr int LDT = 72;   // LDS row pitch (64 + 8 pad) of every 64x64 tile
 constexpr int PLD = 72;   // per-wave P / dS slab pitch
 constexpr float LOG2E = 1.4426950408889634f;
 
-__device__ __forceinline__ void tile_load(short* lds, const bf16_t* g, long ld, int tid) {
+// TAIL (S % 64 != 0): only the first `nrows` (>= 1) rows exist; the others are zero-filled in
+// LDS, not read -- they are MFMA operands, and 0 x (whatever lies behind the tensor) may be NaN.
+template <bool TAIL>
+__device__ __forceinline__ void tile_load(short* lds, const bf16_t* g, long ld, int tid, int nrows) {
   // 64 rows x 64 bf16 (8 chunks of 16 B per row): 512 chunks, 2 per thread
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     const int c = tid + i * 256;
     const int r = c >> 3, col = (c & 7) * 8;
-    *reinterpret_cast<s8v*>(lds + r * LDT + col) = *reinterpret_cast<const s8v*>(g + (long)r * ld + col);
+    if constexpr (TAIL) {
+      // branch-free (the tile's loads stay in flight together): a row past the end loads the
+      // last existing row (nrows >= 1) and is then replaced by zeros
+      const int rr = r < nrows ? r : nrows - 1;
+      s8v v = *reinterpret_cast<const s8v*>(g + (long)rr * ld + col);
+      if (r >= nrows) v = s8v{0, 0, 0, 0, 0, 0, 0, 0};
+      *reinterpret_cast<s8v*>(lds + r * LDT + col) = v;
+    } else {
+      *reinterpret_cast<s8v*>(lds + r * LDT + col) = *reinterpret_cast<const s8v*>(g + (long)r * ld + col);
+    }
   }
+}
+
+// Row of a fragment loaded straight from global memory: the tail variant clamps rows >= S to
+// the last row (such a lane computes a copy of row S - 1; nothing of it is stored).
+template <bool TAIL>
+__device__ __forceinline__ int frag_row(int row, int S) {
+  if constexpr (TAIL) return row < S ? row : S - 1;
+  return row;
 }
 
 // C-layout 16x64 fp32 (4 tiles) -> bf16 slab [16][PLD] of this wave
@@ -85,6 +111,7 @@ struct AttnArgs {
   DropCfg drop;
 };
 
+template <bool TAIL>
 __global__ void __launch_bounds__(256) attn_fwd_kernel(AttnArgs a) {
   __shared__ __attribute__((aligned(16))) short Ks[KB * LDT];
   __shared__ __attribute__((aligned(16))) short Vs[KB * LDT];
@@ -97,7 +124,7 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(AttnArgs a) {
   int klen = a.key_len ? a.key_len[b] : S;
   klen = klen < 1 ? 1 : (klen > S ? S : klen);
   const bf16_t* base = a.qkv + (long)b * S * ldq;
-  const bf16_t* qrow = base + (long)(q0 + (lane & 15)) * ldq + h * D;
+  const bf16_t* qrow = base + (long)frag_row<TAIL>(q0 + (lane & 15), S) * ldq + h * D;
   const bf16x8 qf0 = gfrag(qrow, 0, lane), qf1 = gfrag(qrow, 1, lane);
   const float c2 = a.scale * LOG2E;
   const long bh = (long)b * H + h;
@@ -117,8 +144,8 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(AttnArgs a) {
   for (int kb = 0; kb < nkb; ++kb) {
     const int k0 = kb * KB;
     __syncthreads();
-    tile_load(Ks, base + (long)k0 * ldq + C + h * D, ldq, tid);
-    tile_load(Vs, base + (long)k0 * ldq + 2 * C + h * D, ldq, tid);
+    tile_load<TAIL>(Ks, base + (long)k0 * ldq + C + h * D, ldq, tid, S - k0);
+    tile_load<TAIL>(Vs, base + (long)k0 * ldq + 2 * C + h * D, ldq, tid, S - k0);
     __syncthreads();
     f4v s[4];
 #pragma unroll
@@ -180,7 +207,8 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(AttnArgs a) {
   for (int r = 0; r < 4; ++r) {
     const float lt = grp16_sum(l[r]);
     inv[r] = 1.f / lt;
-    if ((lane & 15) == 0) a.lse[bh * S + q0 + (lane >> 4) * 4 + r] = m[r] + log2f(lt);
+    if ((lane & 15) == 0 && (!TAIL || q0 + (lane >> 4) * 4 + r < S))
+      a.lse[bh * S + q0 + (lane >> 4) * 4 + r] = m[r] + log2f(lt);
   }
   // normalise, stage through the wave slab, 16-B row stores
 #pragma unroll
@@ -193,8 +221,9 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(AttnArgs a) {
   for (int i = 0; i < 2; ++i) {
     const int c = lane + i * 64;  // 16 rows x 8 chunks
     const int r = c >> 3, col = (c & 7) * 8;
-    *reinterpret_cast<s8v*>(a.ctx + ((long)b * S + q0 + r) * C + h * D + col) =
-        *reinterpret_cast<const s8v*>(slab + r * PLD + col);
+    if (!TAIL || q0 + r < S)
+      *reinterpret_cast<s8v*>(a.ctx + ((long)b * S + q0 + r) * C + h * D + col) =
+          *reinterpret_cast<const s8v*>(slab + r * PLD + col);
   }
 }
 
@@ -222,6 +251,7 @@ __global__ void __launch_bounds__(256) attn_bwd_prep_kernel(AttnArgs a) {
   }
 }
 
+template <bool TAIL>
 __global__ void __launch_bounds__(256) attn_bwd_dkv_kernel(AttnArgs a) {
   __shared__ __attribute__((aligned(16))) short Qs[QB * LDT];
   __shared__ __attribute__((aligned(16))) short Gs[QB * LDT];  // dO
@@ -238,8 +268,9 @@ __global__ void __launch_bounds__(256) attn_bwd_dkv_kernel(AttnArgs a) {
   const long bh = (long)b * H + h;
   const uint64_t bhss = (uint64_t)bh * S * S;  // dropout index of element (q, key): bhss + q*S + key
   const bf16_t* base = a.qkv + (long)b * S * ldq;
-  const bf16_t* krow = base + (long)(k0 + (lane & 15)) * ldq + C + h * D;
-  const bf16_t* vrow = base + (long)(k0 + (lane & 15)) * ldq + 2 * C + h * D;
+  const int frow = frag_row<TAIL>(k0 + (lane & 15), S);
+  const bf16_t* krow = base + (long)frow * ldq + C + h * D;
+  const bf16_t* vrow = base + (long)frow * ldq + 2 * C + h * D;
   const bf16x8 kf0 = gfrag(krow, 0, lane), kf1 = gfrag(krow, 1, lane);
   const bf16x8 vf0 = gfrag(vrow, 0, lane), vf1 = gfrag(vrow, 1, lane);
   const float c2 = a.scale * LOG2E;
@@ -249,15 +280,16 @@ __global__ void __launch_bounds__(256) attn_bwd_dkv_kernel(AttnArgs a) {
   short* pslab = Ps[wave];
   short* dslab = Ds[wave];
   const bool any_valid = blockIdx.x * KB < klen;
-  const int nqb = any_valid ? S / QB : 0;
+  const int nqb = any_valid ? (TAIL ? (S + QB - 1) / QB : S / QB) : 0;
   for (int qb = 0; qb < nqb; ++qb) {
     const int q0 = qb * QB;
     __syncthreads();
-    tile_load(Qs, base + (long)q0 * ldq + h * D, ldq, tid);
-    tile_load(Gs, a.dout + ((long)b * S + q0) * C + h * D, C, tid);
+    tile_load<TAIL>(Qs, base + (long)q0 * ldq + h * D, ldq, tid, S - q0);
+    tile_load<TAIL>(Gs, a.dout + ((long)b * S + q0) * C + h * D, C, tid, S - q0);
     if (tid < QB) {
-      lse_s[tid] = a.lse[bh * S + q0 + tid];
-      dv_s[tid] = a.dvec[bh * S + q0 + tid];
+      const bool live = !TAIL || q0 + tid < S;  // queries >= S: no lse / Dv entry exists
+      lse_s[tid] = live ? a.lse[bh * S + q0 + tid] : 0.f;
+      dv_s[tid] = live ? a.dvec[bh * S + q0 + tid] : 0.f;
     }
     __syncthreads();
     // S^T: rows = keys (this wave), cols = queries
@@ -276,10 +308,11 @@ __global__ void __launch_bounds__(256) attn_bwd_dkv_kernel(AttnArgs a) {
     for (int t = 0; t < 4; ++t) {
       const int qi = t * 16 + (lane & 15);
       const float ls = lse_s[qi], dvq = dv_s[qi];
+      const bool qlive = !TAIL || q0 + qi < S;  // a query column >= S adds p = dS = 0
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int key = k0 + (lane >> 4) * 4 + r;
-        const float pr = key < klen ? exp2f(p[t][r] * c2 - ls) : 0.f;
+        const float pr = (key < klen && qlive) ? exp2f(p[t][r] * c2 - ls) : 0.f;
         const float mul = a.drop.on ? drop_mul(a.drop, bhss + (uint32_t)((q0 + qi) * S + key)) : 1.f;
         pd[t][r] = pr * mul;
         ds[t][r] = pr * (dp[t][r] * mul - dvq);
@@ -312,14 +345,20 @@ __global__ void __launch_bounds__(256) attn_bwd_dkv_kernel(AttnArgs a) {
   for (int i = 0; i < 2; ++i) {
     const int c = lane + i * 64;
     const int r = c >> 3, col = (c & 7) * 8;
-    *reinterpret_cast<s8v*>(drow + (long)r * ldq + C + h * D + col) =
-        *reinterpret_cast<const s8v*>(pslab + r * PLD + col);
-    *reinterpret_cast<s8v*>(drow + (long)r * ldq + 2 * C + h * D + col) =
-        *reinterpret_cast<const s8v*>(dslab + r * PLD + col);
+    if (!TAIL || k0 + r < S) {
+      *reinterpret_cast<s8v*>(drow + (long)r * ldq + C + h * D + col) =
+          *reinterpret_cast<const s8v*>(pslab + r * PLD + col);
+      *reinterpret_cast<s8v*>(drow + (long)r * ldq + 2 * C + h * D + col) =
+          *reinterpret_cast<const s8v*>(dslab + r * PLD + col);
+    }
   }
 }
 
-__global__ void __launch_bounds__(256) attn_bwd_dq_kernel(AttnArgs a) {
+// (the tail variant's few extra index registers would cost the third wave per SIMD that the
+// non-tail one gets unasked: 174 against 168 registers; "1" is the default)
+template <bool TAIL>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TAIL ? 3 : 1)))
+attn_bwd_dq_kernel(AttnArgs a) {
   __shared__ __attribute__((aligned(16))) short Ks[KB * LDT];
   __shared__ __attribute__((aligned(16))) short Vs[KB * LDT];
   __shared__ __attribute__((aligned(16))) short Ds[4][16 * PLD];
@@ -333,15 +372,16 @@ __global__ void __launch_bounds__(256) attn_bwd_dq_kernel(AttnArgs a) {
   const long bh = (long)b * H + h;
   const uint64_t bhss = (uint64_t)bh * S * S;  // dropout index of element (q, key): bhss + q*S + key
   const bf16_t* base = a.qkv + (long)b * S * ldq;
-  const bf16_t* qrow = base + (long)(q0 + (lane & 15)) * ldq + h * D;
+  const bf16_t* qrow = base + (long)frag_row<TAIL>(q0 + (lane & 15), S) * ldq + h * D;
   const bf16_t* grow = a.dout + ((long)b * S + q0 + (lane & 15)) * C + h * D;
+  if constexpr (TAIL) grow = a.dout + ((long)b * S + frag_row<TAIL>(q0 + (lane & 15), S)) * C + h * D;
   const bf16x8 qf0 = gfrag(qrow, 0, lane), qf1 = gfrag(qrow, 1, lane);
   const bf16x8 gf0 = gfrag(grow, 0, lane), gf1 = gfrag(grow, 1, lane);
   const float c2 = a.scale * LOG2E;
   float ls[4], dvq[4];
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    const int q = q0 + (lane >> 4) * 4 + r;
+    const int q = frag_row<TAIL>(q0 + (lane >> 4) * 4 + r, S);
     ls[r] = a.lse[bh * S + q];
     dvq[r] = a.dvec[bh * S + q];
   }
@@ -353,8 +393,8 @@ __global__ void __launch_bounds__(256) attn_bwd_dq_kernel(AttnArgs a) {
   for (int kb = 0; kb < nkb; ++kb) {
     const int k0 = kb * KB;
     __syncthreads();
-    tile_load(Ks, base + (long)k0 * ldq + C + h * D, ldq, tid);
-    tile_load(Vs, base + (long)k0 * ldq + 2 * C + h * D, ldq, tid);
+    tile_load<TAIL>(Ks, base + (long)k0 * ldq + C + h * D, ldq, tid, S - k0);
+    tile_load<TAIL>(Vs, base + (long)k0 * ldq + 2 * C + h * D, ldq, tid, S - k0);
     __syncthreads();
     f4v s[4], dp[4];
 #pragma unroll
@@ -397,8 +437,9 @@ __global__ void __launch_bounds__(256) attn_bwd_dq_kernel(AttnArgs a) {
   for (int i = 0; i < 2; ++i) {
     const int c = lane + i * 64;
     const int r = c >> 3, col = (c & 7) * 8;
-    *reinterpret_cast<s8v*>(a.dqkv + ((long)b * S + q0 + r) * ldq + h * D + col) =
-        *reinterpret_cast<const s8v*>(dslab + r * PLD + col);
+    if (!TAIL || q0 + r < S)
+      *reinterpret_cast<s8v*>(a.dqkv + ((long)b * S + q0 + r) * ldq + h * D + col) =
+          *reinterpret_cast<const s8v*>(dslab + r * PLD + col);
   }
 }
 
@@ -710,7 +751,7 @@ __global__ void __launch_bounds__(SQ * 4) attn_fwd_short_kernel(AttnArgs a) {
   stage_store(slab, o, a.ctx + ((long)b * SQ + q0) * C + h * D, C, lane);
 }
 
-bool shape_ok(int S, int H) { return S > 0 && S % 64 == 0 && H > 0; }
+bool shape_ok(int S, int H) { return S > 0 && H > 0; }
 
 // CLOUD_AMD_ATTN_FUSED_BWD=0 keeps the three-kernel backward at S <= 128 (A/B runs)
 bool fused_bwd_enabled() {
@@ -739,7 +780,9 @@ int ca_attn_fwd(const bf16_t* qkv, bf16_t* ctx, float* lse, const int* key_len, 
     CA_LAUNCH_CHECK();
     return 0;
   }
-  attn_fwd_kernel<<<dim3(S / QB, H, B), 256, 0, s>>>(a);
+  const dim3 grid((S + QB - 1) / QB, H, B);
+  if (S % QB) attn_fwd_kernel<true><<<grid, 256, 0, s>>>(a);
+  else attn_fwd_kernel<false><<<grid, 256, 0, s>>>(a);
   CA_LAUNCH_CHECK();
   return 0;
 }
@@ -761,9 +804,13 @@ int ca_attn_bwd(const bf16_t* qkv, const bf16_t* out, const bf16_t* dout, const 
   const long rows = (long)B * S * H;
   attn_bwd_prep_kernel<<<ca_cdiv(rows, 32), 256, 0, s>>>(a);
   CA_LAUNCH_CHECK();
-  attn_bwd_dkv_kernel<<<dim3(S / KB, H, B), 256, 0, s>>>(a);
+  static_assert(QB == KB, "one grid for the key-block and the query-block kernels");
+  const dim3 grid((S + QB - 1) / QB, H, B);
+  if (S % QB) attn_bwd_dkv_kernel<true><<<grid, 256, 0, s>>>(a);
+  else attn_bwd_dkv_kernel<false><<<grid, 256, 0, s>>>(a);
   CA_LAUNCH_CHECK();
-  attn_bwd_dq_kernel<<<dim3(S / QB, H, B), 256, 0, s>>>(a);
+  if (S % QB) attn_bwd_dq_kernel<true><<<grid, 256, 0, s>>>(a);
+  else attn_bwd_dq_kernel<false><<<grid, 256, 0, s>>>(a);
   CA_LAUNCH_CHECK();
   return 0;
 }
