@@ -110,7 +110,10 @@ _VARS = [
         "stages 2-4)", "bench"),
     Var("CLOUD_AMD_EPI_PF", bool, True, "GEMM epilogues that read memory or run an activation (BN-statistics "
         "and inference-BN forward 1x1 convs, BERT bias/GELU/GELU'/beta dense layers): 4 staged output rows in flight per trip", "ops"),
-    Var("CLOUD_AMD_ATTN_FUSED_BWD", bool, True, "attention at S = 64 / 128: one workgroup per (batch, head) for "
+    Var("CLOUD_AMD_EPI_PIPE", bool, True, "input-gradient GEMMs / convolutions with the BN-backward statistics "
+        "epilogue: the next two output rows' operand loads are in flight under this pair's arithmetic and stores "
+        "(ca_mfma_core.h gemm_epilogue); 0 = one pair at a time (A/B runs)", "ops"),
+    Var("CLOUD_AMD_ATTN_FUSED_BWD", bool, True,"attention at S = 64 / 128: one workgroup per (batch, head) for "
         "the forward and a single fused backward kernel; 0 keeps the 64-query-block kernels", "ops"),
     Var("CLOUD_AMD_CONV_HALO_WGRAD", bool, True, "the weight gradient of the same 3x3 / 64-channel / width-56 "
         "convolutions on the LDS-resident kernel (ca_conv_halo.h conv3x3_halo_wgrad: 64 x 576 partial in registers, "

@@ -667,7 +667,9 @@ __device__ __forceinline__ void mfma_gemm_xa_dw(const CoreParams& P, const XaPar
       lgkm_wait0();
       bar256();
       if (t == KS - 1) {  // dx chunk nc complete
-        gemm_epilogue<BM, BN, WM, WN, EPI, EPI_SH, 1>(P, acc, Bs, m0, nc * BN, tm, tid);
+        // (one-batch row pass: the weight-gradient accumulators stay live across this epilogue, and
+        // a second batch of operands spills)
+        gemm_epilogue<BM, BN, WM, WN, EPI, EPI_SH, 1, FM, FN, false, false, false>(P, acc, Bs, m0, nc * BN, tm, tid);
         __syncthreads();
 #pragma unroll
         for (int i = 0; i < FM; ++i)

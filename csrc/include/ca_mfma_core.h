@@ -105,6 +105,7 @@ struct CoreParams {
   // optionally kept (preact), or, in the backward, C = acc * act'(dact_src).
   const float* bias;      // [N] fp32 or null
   int act;                // ACT_* below
+  int epi_pipe;           // BN-backward statistics epilogues: pipelined row pass (epi_pipe_enabled)
   bf16_t* preact;         // [M][ld_aux] or null
   const bf16_t* dact_src; // [M][ld_aux] or null (backward: multiply by act'(src))
   long ld_aux;
@@ -296,6 +297,14 @@ inline int split_xcd_enabled() {
   return on;
 }
 
+// host: CLOUD_AMD_EPI_PIPE=0 keeps the one-batch-at-a-time row pass of the BN-backward
+// statistics epilogues (gemm_epilogue; A/B runs).  Read once; base_params / conv_params copy it
+// into CoreParams::epi_pipe.
+inline int epi_pipe_enabled() {
+  static const bool on = env_switch("CLOUD_AMD_EPI_PIPE", true);
+  return on;
+}
+
 struct BlkPos {
   int tile, split;
 };
@@ -433,13 +442,18 @@ __device__ __forceinline__ void mfma_acc(f4v (&acc)[FM][FN], const bf16x8 (&af)[
       acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[j], af[i], acc[i][j], 0, 0, 0);
 }
 
+// 16-B zero page: source of out-of-range chunks (pointer-mode loaders) and base of empty buffer
+// resources
+static __device__ __attribute__((aligned(16))) bf16_t ca_zero16[8];
+
 // Shared epilogue: fp32 split-K slab store, or bf16 through LDS with bias /
 // activation / pre-activation / act' / beta-accumulate / BN-statistics options.
 // EPF > 1: plain / statistics bf16 epilogues read EPF staged rows from LDS before
 // storing any (batched LDS latency; dense GEMMs only -- the conv loaders' registers leave
 // no room, see docs/performance.md)
+// ROWPIPE = false: a core without the registers for the pipelined BN-statistics row pass (below)
 template <int BM, int BN, int WM, int WN, int EPI, int SMEM_SHORTS, int EPF = 1, int FM = BM / WM / 16,
-          int FN = BN / WN / 16, bool QUAD = false, bool BIAS_IN_ACC = false>
+          int FN = BN / WN / 16, bool QUAD = false, bool BIAS_IN_ACC = false, bool ROWPIPE = true>
 __device__ __forceinline__ void gemm_epilogue(const CoreParams& P, f4v (&acc)[FM][FN], short* smem, int m0, int n0,
                                               int tm, int tid) {
   constexpr int NT = WM * WN * 64;
@@ -470,6 +484,96 @@ __device__ __forceinline__ void gemm_epilogue(const CoreParams& P, f4v (&acc)[FM
     return;
   } else {
     short* Cs = smem;
+    // Each thread owns one 8-column group (NT is a multiple of BN/8) and walks IT rows.
+    // The global reads of the epilogue (old C for beta, BN input z and ReLU mask for
+    // the BN-backward statistics) are issued PF rows at a time before any is used, so
+    // a tile pays ceil(IT/PF) memory round trips instead of IT.
+    constexpr int CH = BM * BN / 8;
+    static_assert(CH % NT == 0, "epilogue chunks must divide the threads");
+    constexpr int IT = CH / NT;
+    constexpr bool Z2 = EPI == EPI_BF16_BNR2;
+    constexpr bool BNS = EPI == EPI_BF16_BN || EPI == EPI_BF16_BNR || Z2, STS = EPI == EPI_BF16_ST;
+    constexpr bool RSTAT = BNS || STS;
+    constexpr bool RES = EPI != EPI_BF16_BN;  // res_src / res_mask compiled in
+    constexpr int PF = BNS ? (IT < 2 ? IT : 2) : (IT < EPF ? IT : EPF);
+    // FIXCOL: NT is a multiple of BN / 8, so a thread keeps one 8-column group for every row it
+    // walks (the statistics epilogues need that); otherwise (BN = 96 on 256 threads, plain
+    // epilogues only) the column group follows the chunk index
+    constexpr bool FIXCOL = NT % (BN / 8) == 0;
+
+    // Pipelined row pass of the BN-backward statistics kinds (CoreParams::epi_pipe): batch b+1's
+    // global loads are issued before batch b's LDS reads, arithmetic and stores, and batch 0's
+    // right here -- none depends on the accumulators -- so their round trip runs under the
+    // staging of the tile and the barrier.  Two batches live in registers (pa / pb).  Same rows,
+    // same column group, same order of additions per thread as the one-batch pass below: outputs
+    // and partials are bit for bit the same.
+    //   * Every access goes through buffer resources based at the tile's first output row with a
+    //     32-bit byte offset per row (one register serves old C / res_src, z, z2 and the store,
+    //     which share the [rows][ldc] layout); a row or source that the one-batch pass would not
+    //     read gets the offset PIPE_OOB, beyond num_records: the hardware returns zeros without
+    //     touching memory, and drops a store.  So every thread issues the same vector-memory
+    //     stream whatever its predicates and the compiler's vmcnt waits stay counted (a load or
+    //     store behind a branch makes the waitcnt pass drain to vmcnt(0)).
+    //   * Absent sources (null masks, beta 0) are resources with num_records 0.
+    //   * A tile whose output rows span 2 GiB or more (only an extreme ldc), and the dense-layer
+    //     options (activation, preact, dact_src), keep the one-batch pass.
+    constexpr int NB = IT / PF;
+    constexpr bool PIPE = ROWPIPE && BNS && FIXCOL && NB >= 2 && NB % 2 == 0;
+    constexpr uint32_t PIPE_OOB = 0x80000000u;
+    constexpr int PPF = PIPE ? PF : 1;
+    struct PipeBatch {
+      s8v o[PPF], z[PPF], z2[Z2 ? PPF : 1];
+      uint8_t bm[PPF], rm[RES ? PPF : 1];  // (bytes as loaded: widening them here would wait for the load)
+      uint32_t off[PPF];  // byte offset of the row's 8-column group, or PIPE_OOB (row not stored)
+    };
+    PipeBatch pa, pb;
+    (void)pa;
+    (void)pb;
+    bool pipe = false;
+    if constexpr (PIPE) {
+      const bool fx0 = P.act != ACT_NONE || P.dact_src != nullptr || P.preact != nullptr;
+      const int mlast = (m0 + BM < P.M ? m0 + BM : P.M) - 1;
+      pipe = P.epi_pipe && !fx0 && m0 < P.M &&
+             (out_row(P, mlast) - out_row(P, m0) + 1) * P.ldc * 2 < (long)BUF_CAP;
+    }
+    const long orow0 = pipe ? out_row(P, m0) : 0;
+    const bool pbeta = P.beta != 0.f;
+    const int pcol0 = (tid % (BN / 8)) * 8, pn8 = P.N / 8;
+    auto pipe_rsrc = [&](const void* p, long stride_bytes, bool present) {
+      const bool on = pipe && present && p != nullptr;
+      return __builtin_amdgcn_make_buffer_rsrc(
+          on ? const_cast<char*>(reinterpret_cast<const char*>(p)) + orow0 * stride_bytes
+             : reinterpret_cast<char*>(ca_zero16),
+          (short)0, on ? (int)BUF_CAP : 0, 0x00020000);
+    };
+    const auto prs_c = pipe_rsrc(P.C, P.ldc * 2, true);
+    const auto prs_o = pipe_rsrc((RES && P.res_src) ? (const void*)P.res_src : (const void*)P.C, P.ldc * 2, pbeta);
+    const auto prs_z = pipe_rsrc(P.bnz, P.ldc * 2, true);
+    const auto prs_z2 = pipe_rsrc(P.bnz2, P.ldc * 2, Z2);
+    const auto prs_bm = pipe_rsrc(P.bnmask, pn8, true);
+    const auto prs_rm = pipe_rsrc(P.res_mask, pn8, RES && pbeta);
+    auto pipe_issue = [&](int it0, PipeBatch& B, bool live) {
+#pragma unroll
+      for (int u = 0; u < PPF; ++u) {
+        const int gm = m0 + tid / (BN / 8) + (it0 + u) * (NT / (BN / 8));
+        const int gn = n0 + pcol0;
+        const bool ok = live && gm < P.M && gn < P.N;
+        const long orow = ok ? out_row(P, gm) : orow0;
+        const uint32_t rel = (uint32_t)(orow - orow0);
+        const uint32_t off = ok ? (rel * (uint32_t)P.ldc + (uint32_t)gn) * 2u : PIPE_OOB;
+        const uint32_t moff = ok ? rel * (uint32_t)pn8 + ((uint32_t)gn >> 3) : PIPE_OOB;
+        B.off[u] = off;
+        B.o[u] = __builtin_bit_cast(s8v, __builtin_amdgcn_raw_buffer_load_b128(
+                                             prs_o, (int)((ok && beta_row_stored(P, orow)) ? off : PIPE_OOB), 0, 0));
+        if constexpr (RES) B.rm[u] = __builtin_amdgcn_raw_buffer_load_b8(prs_rm, (int)moff, 0, 0);
+        B.z[u] = __builtin_bit_cast(s8v, __builtin_amdgcn_raw_buffer_load_b128(prs_z, (int)off, 0, 0));
+        B.bm[u] = __builtin_amdgcn_raw_buffer_load_b8(prs_bm, (int)moff, 0, 0);
+        if constexpr (Z2) B.z2[u] = __builtin_bit_cast(s8v, __builtin_amdgcn_raw_buffer_load_b128(prs_z2, (int)off, 0, 0));
+      }
+    };
+    if constexpr (PIPE) {
+      if (pipe) pipe_issue(0, pa, true);
+    }
     if constexpr (EPI == EPI_BF16_AFF) {  // BN affine: one fp32 FMA per accumulator
 #pragma unroll
       for (int j = 0; j < FN; ++j) {
@@ -548,32 +652,61 @@ __device__ __forceinline__ void gemm_epilogue(const CoreParams& P, f4v (&acc)[FM
     float bsum[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, bzsum[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     (void)bsum;
     (void)bzsum;
-    // Each thread owns one 8-column group (NT is a multiple of BN/8) and walks IT rows.
-    // The global reads of the epilogue (old C for beta, BN input z and ReLU mask for
-    // the BN-backward statistics) are issued PF rows at a time before any is used, so
-    // a tile pays ceil(IT/PF) memory round trips instead of IT.
-    constexpr int CH = BM * BN / 8;
-    static_assert(CH % NT == 0, "epilogue chunks must divide the threads");
-    constexpr int IT = CH / NT;
-    constexpr bool Z2 = EPI == EPI_BF16_BNR2;
-    constexpr bool BNS = EPI == EPI_BF16_BN || EPI == EPI_BF16_BNR || Z2, STS = EPI == EPI_BF16_ST;
-    constexpr bool RSTAT = BNS || STS;
     float bz2sum[Z2 ? 8 : 1];
 #pragma unroll
     for (int j = 0; j < (Z2 ? 8 : 1); ++j) bz2sum[j] = 0.f;
-    constexpr bool RES = EPI != EPI_BF16_BN;  // res_src / res_mask compiled in
     // the calling core's LDS (SMEM_SHORTS bf16 slots) must hold the three statistics rows
     static_assert(!Z2 || 3 * (NT / (BN / 8)) * BN * 4 <= 2 * SMEM_SHORTS, "three statistics rows must fit the LDS");
-    constexpr int PF = BNS ? (IT < 2 ? IT : 2) : (IT < EPF ? IT : EPF);
-    // FIXCOL: NT is a multiple of BN / 8, so a thread keeps one 8-column group for every row it
-    // walks (the statistics epilogues need that); otherwise (BN = 96 on 256 threads, plain
-    // epilogues only) the column group follows the chunk index
-    constexpr bool FIXCOL = NT % (BN / 8) == 0;
     static_assert(FIXCOL || (!RSTAT && EPI == EPI_BF16), "column groups must divide the threads");
     const int col0 = (tid % (BN / 8)) * 8;
     const bool has_beta = P.beta != 0.f;
+    if constexpr (PIPE) {
+      if (pipe) {
+        // rows of batch B (first row index it0): LDS read, beta term, store, statistics
+        auto pipe_rows = [&](int it0, const PipeBatch& B) {
+#pragma unroll
+          for (int u = 0; u < PPF; ++u) {
+            const uint32_t off = B.off[u];
+            const bool ok = off != PIPE_OOB;
+            s8v v = zero8();
+            uint32_t mk = 0;
+            if (ok) {
+              const int row = tid / (BN / 8) + (it0 + u) * (NT / (BN / 8));
+              v = *reinterpret_cast<const s8v*>(Cs + EL::idx(row, col0));
+              mk = P.bnmask ? B.bm[u] : 0xffu;
+              if (has_beta) {
+                uint32_t rmk = 0xffu;
+                if constexpr (RES) rmk = P.res_mask ? B.rm[u] : 0xffu;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                  const float o = ((rmk >> j) & 1u) ? bf2f((bf16_t)B.o[u][j]) : 0.f;
+                  v[j] = (short)f2bf(bf2f((bf16_t)v[j]) + P.beta * o);
+                }
+              }
+            }
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), prs_c, (int)off, 0, 0);
+            if (ok) {
+#pragma unroll
+              for (int j = 0; j < 8; ++j) {
+                const float g = ((mk >> j) & 1u) ? bf2f((bf16_t)v[j]) : 0.f;
+                bsum[j] += g;
+                bzsum[j] += g * bf2f((bf16_t)B.z[u][j]);
+                if constexpr (Z2) bz2sum[j] += g * bf2f((bf16_t)B.z2[u][j]);
+              }
+            }
+          }
+        };
 #pragma unroll 1
-    for (int it0 = 0; it0 < IT; it0 += PF) {
+        for (int b = 0; b < NB; b += 2) {
+          pipe_issue((b + 1) * PF, pb, true);
+          pipe_rows(b * PF, pa);
+          pipe_issue((b + 2) * PF, pa, b + 2 < NB);  // past the last batch: every offset out of range
+          pipe_rows((b + 1) * PF, pb);
+        }
+      }
+    }
+#pragma unroll 1
+    for (int it0 = pipe ? IT : 0; it0 < IT; it0 += PF) {
       s8v opre[PF], zpre[BNS ? PF : 1], zpre2[Z2 ? PF : 1], dsrc[RSTAT ? 1 : PF];
       uint32_t mk[PF];  // bits 0-7: BN ReLU mask (BN-backward statistics), bits 8-15: res_mask
       long orow[PF];
@@ -852,8 +985,6 @@ __device__ __forceinline__ void mfma_gemm_body(const CoreParams& P) {
 // Out-of-range K chunks read a 16-B zero page (rows/cols beyond M/N are clamped:
 // they only feed outputs that are never stored).  One LDS stage, two barriers
 // per K step; several blocks per CU hide the DMA latency.
-
-static __device__ __attribute__((aligned(16))) bf16_t ca_zero16[8];
 
 typedef __attribute__((address_space(3))) void lds_void;
 

@@ -1010,6 +1010,7 @@ CoreParams conv_params(int Nb, int H, int W, int Cin, int Cout, int KH, int KW, 
   p.div_cin = make_fastdiv(Cin); p.div_cout = make_fastdiv(Cout); p.div_kw = make_fastdiv(KW);
   p.cin_tile = (Cin % BK == 0) ? 1 : 0;
   p.cout_tile = (Cout % BK == 0) ? 1 : 0;
+  p.epi_pipe = epi_pipe_enabled();
   return p;
 }
 

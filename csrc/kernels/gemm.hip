@@ -601,6 +601,7 @@ CoreParams base_params(const bf16_t* A, long lda, const bf16_t* B, long ldb, voi
   CoreParams p{};
   p.A = A; p.lda = lda; p.B = B; p.ldb = ldb; p.C = C; p.ldc = ldc;
   p.M = M; p.N = N; p.K = K; p.k_per_split = K;
+  p.epi_pipe = epi_pipe_enabled();
   return p;
 }
 
