@@ -18,7 +18,7 @@ from ..ops.dense import conv2d as conv_act_op
 from ..ops.dense import dense as dense_op
 from ..ops.dropout import dropout as dropout_op
 from . import activations, initializers, regularizers
-from .engine import Input, InputLayer, Layer, global_policy  # noqa: F401
+from .engine import Input, InputLayer, KerasTensor, Layer, global_policy  # noqa: F401
 
 
 def _pair(v):
@@ -363,6 +363,178 @@ class Concatenate(Layer):
         return c
 
 
+class MultiHeadAttention(Layer):
+    """``tf.keras.layers.MultiHeadAttention`` with ``value_dim == key_dim`` and the default
+    output shape and attention axes.
+
+    Weights are packed for the kernels, in the ``[units, fan_in]`` layout of ``Dense``:
+    ``qkv_kernel [3*H*key_dim, dim]`` (Q | K | V, head ``h`` at rows ``h*key_dim`` of each third)
+    with ``qkv_bias``, and ``out_kernel [dim, H*key_dim]`` with ``out_bias``.
+    ``get_weights`` / ``set_weights`` present Keras's arrays in Keras's order and shapes (query,
+    key, value kernels ``[dim, H, key_dim]`` with biases ``[H, key_dim]``, output kernel
+    ``[H, key_dim, dim]`` with bias ``[dim]``), so weights copied from a Keras model give the
+    same function.
+
+    Self-attention (``query is value``, no ``key`` or the same tensor) without an
+    ``attention_mask`` and without ``return_attention_scores`` is one packed projection,
+    ``ops.attention`` and the output projection: under the mixed policy with ``key_dim == 64``
+    all three run on the in-tree kernels, forward and backward.  Everything else
+    (cross-attention, an explicit mask, returned scores) is the same math in PyTorch.
+
+    Calls: Keras style ``layer(query, value, key=None, attention_mask=None,
+    use_causal_mask=False, return_attention_scores=False, training=None)``, or the list form
+    of ``Add`` / ``Concatenate``, ``layer([query, value])`` / ``layer([query, value, key])``.
+    The functional graph replays ``layer(inputs, training=...)`` only, so causality also lives
+    on the layer (``use_causal_mask`` constructor argument, kept by ``get_config``); a symbolic
+    ``layer(x, x, use_causal_mask=True)`` records the flag on the layer.
+    """
+
+    def __init__(self, num_heads, key_dim, value_dim=None, dropout=0.0, use_bias=True, output_shape=None,
+                 attention_axes=None, kernel_initializer="glorot_uniform", use_causal_mask=False, **kw):
+        super().__init__(**kw)
+        self.num_heads, self.key_dim = int(num_heads), int(key_dim)
+        if value_dim is not None and int(value_dim) != self.key_dim:
+            raise ValueError(f"MultiHeadAttention: value_dim must equal key_dim ({self.key_dim}), got {value_dim}")
+        if output_shape is not None:
+            raise ValueError("MultiHeadAttention: output_shape is not supported (the output has the query's width)")
+        if attention_axes is not None:
+            raise ValueError("MultiHeadAttention: attention_axes is not supported (attention runs over axis 1)")
+        self.dropout = float(dropout)
+        self.use_bias = use_bias
+        self.kernel_initializer = kernel_initializer
+        self.use_causal_mask = bool(use_causal_mask)
+
+    def build(self, input_shape):
+        shapes = input_shape if isinstance(input_shape, list) else [input_shape]
+        dim = int(shapes[0][-1])
+        if any(int(s[-1]) != dim for s in shapes[1:]):
+            raise ValueError("MultiHeadAttention: query, value and key must have the same width "
+                             f"(the projections are packed), got {[tuple(s) for s in shapes]}")
+        hd = self.num_heads * self.key_dim
+        init = initializers.get(self.kernel_initializer)
+        thirds = [torch.empty(hd, dim) for _ in range(3)]
+        for t in thirds:
+            init(t)
+        self.qkv_kernel = torch.nn.Parameter(torch.cat(thirds, 0).to(self.compute_dtype))
+        wo = torch.empty(dim, hd)
+        init(wo)
+        self.out_kernel = torch.nn.Parameter(wo.to(self.compute_dtype))
+        if self.use_bias:
+            self.qkv_bias = torch.nn.Parameter(torch.zeros(3 * hd, dtype=_bias_dtype(self)))
+            self.out_bias = torch.nn.Parameter(torch.zeros(dim, dtype=_bias_dtype(self)))
+        else:
+            self.qkv_bias = self.out_bias = None
+
+    def __call__(self, query, value=None, key=None, attention_mask=None, use_causal_mask=False,
+                 return_attention_scores=False, training=None):
+        if isinstance(query, (list, tuple)):
+            if value is not None or key is not None:
+                raise ValueError("MultiHeadAttention: pass either [query, value(, key)] or query, value(, key)")
+            if len(query) not in (2, 3):
+                raise ValueError("MultiHeadAttention: the list form is [query, value] or [query, value, key]")
+            query, value, key = (*query, None)[:3]
+        elif value is None:
+            raise ValueError("MultiHeadAttention: value is required")
+        ins, seen = [], {}
+        for t in (query, value) + ((key,) if key is not None else ()):
+            if id(t) not in seen:  # the same object stays the same object: that is what selects self-attention
+                seen[id(t)] = self._convert_inputs(t)
+            ins.append(seen[id(t)])
+        if all(isinstance(t, KerasTensor) for t in ins):
+            if attention_mask is not None or return_attention_scores:
+                raise ValueError("MultiHeadAttention: attention_mask and return_attention_scores need an eager "
+                                 "call (the functional graph replays layer(inputs, training=...) only)")
+            if use_causal_mask:
+                self.use_causal_mask = True
+            return super().__call__(ins)
+        return super().__call__(ins, attention_mask=attention_mask, use_causal_mask=use_causal_mask,
+                                return_attention_scores=return_attention_scores, training=training)
+
+    def call(self, inputs, training=None, attention_mask=None, use_causal_mask=False, return_attention_scores=False):
+        query, value = inputs[0], inputs[1]
+        key = inputs[2] if len(inputs) > 2 else value
+        causal = self.use_causal_mask or bool(use_causal_mask)
+        H, D = self.num_heads, self.key_dim
+        hd = H * D
+        p = self.dropout if training else 0.0
+        dt = self.qkv_kernel.dtype
+        if query is value and key is value and attention_mask is None and not return_attention_scores:
+            qkv = dense_op(query.to(dt), self.qkv_kernel, self.qkv_bias, None)
+            ctx = ops.attention(qkv, H, None, p, bool(training), causal=causal)
+            return dense_op(ctx, self.out_kernel, self.out_bias, None)
+
+        def proj(x, i):
+            b = None if self.qkv_bias is None else self.qkv_bias[i * hd:(i + 1) * hd]
+            y = dense_op(x.to(dt), self.qkv_kernel[i * hd:(i + 1) * hd], b, None)
+            return y.float().reshape(y.shape[0], y.shape[1], H, D).transpose(1, 2)  # [B, H, len, D]
+
+        q, k, v = proj(query, 0), proj(key, 1), proj(value, 2)
+        T, S = q.shape[2], k.shape[2]
+        att = (q @ k.transpose(-1, -2)) * (1.0 / math.sqrt(D))
+        allowed = None
+        if attention_mask is not None:
+            allowed = torch.as_tensor(attention_mask, device=att.device).bool()
+            while allowed.dim() < 3:
+                allowed = allowed[None]
+            if allowed.dim() == 3:
+                allowed = allowed[:, None]  # heads
+        if causal:
+            tri = torch.ones(T, S, dtype=torch.bool, device=att.device).tril()
+            allowed = tri if allowed is None else allowed & tri
+        if allowed is not None:
+            att = att.masked_fill(~allowed, torch.finfo(att.dtype).min)
+        scores = att.softmax(-1)
+        pd = F.dropout(scores, p, training=True) if p > 0 else scores
+        ctx = (pd @ v).transpose(1, 2).reshape(q.shape[0], T, hd).to(dt)
+        out = dense_op(ctx, self.out_kernel, self.out_bias, None)
+        return (out, scores) if return_attention_scores else out
+
+    def compute_output_shape(self, input_shape):
+        self._maybe_build(input_shape)
+        return tuple(input_shape[0])
+
+    def get_weights(self):
+        H, D = self.num_heads, self.key_dim
+        hd = H * D
+        w = self.qkv_kernel.detach().float().cpu()
+        dim = w.shape[1]
+        out = []
+        for i in range(3):
+            out.append(w[i * hd:(i + 1) * hd].t().reshape(dim, H, D).contiguous().numpy())
+            if self.use_bias:
+                out.append(self.qkv_bias.detach().float().cpu()[i * hd:(i + 1) * hd].reshape(H, D).numpy())
+        out.append(self.out_kernel.detach().float().cpu().t().reshape(H, D, dim).contiguous().numpy())
+        if self.use_bias:
+            out.append(self.out_bias.detach().float().cpu().numpy())
+        return out
+
+    def set_weights(self, weights):
+        import numpy as np
+
+        n = 8 if self.use_bias else 4
+        if len(weights) != n:
+            raise ValueError(f"expected {n} weight arrays, got {len(weights)}")
+        hd = self.num_heads * self.key_dim
+        ws = [torch.as_tensor(np.asarray(w)).float() for w in weights]
+        step = 2 if self.use_bias else 1
+        dim = self.qkv_kernel.shape[1]
+        with torch.no_grad():
+            for i in range(3):
+                self.qkv_kernel[i * hd:(i + 1) * hd].copy_(ws[i * step].reshape(dim, hd).t())
+                if self.use_bias:
+                    self.qkv_bias[i * hd:(i + 1) * hd].copy_(ws[i * step + 1].reshape(hd))
+            self.out_kernel.copy_(ws[3 * step].reshape(hd, dim).t())
+            if self.use_bias:
+                self.out_bias.copy_(ws[3 * step + 1].reshape(dim))
+
+    def get_config(self):
+        c = super().get_config()
+        c.update(num_heads=self.num_heads, key_dim=self.key_dim, dropout=self.dropout, use_bias=self.use_bias,
+                 kernel_initializer=self.kernel_initializer if isinstance(self.kernel_initializer, str)
+                 else "glorot_uniform", use_causal_mask=self.use_causal_mask)
+        return c
+
+
 # ---- augmentation (K11): active only in training ------------------------------
 class RandomFlip(Layer):
     def __init__(self, mode="horizontal", seed=None, **kw):
@@ -521,7 +693,8 @@ class TorchModule(Layer):
 LAYERS = {cls.__name__: cls for cls in [
     Dense, Conv2D, MaxPooling2D, AveragePooling2D, GlobalAveragePooling2D, GlobalMaxPooling2D, Flatten, Reshape,
     Dropout, Activation, ReLU, Softmax, BatchNormalization, LayerNormalization, Embedding, Rescaling, Add,
-    Concatenate, RandomFlip, RandomRotation, RandomTranslation, RandomZoom, RandomContrast, InputLayer]}
+    Concatenate, MultiHeadAttention, RandomFlip, RandomRotation, RandomTranslation, RandomZoom, RandomContrast,
+    InputLayer]}
 MaxPool2D = MaxPooling2D
 AvgPool2D = AveragePooling2D
 GlobalAvgPool2D = GlobalAveragePooling2D

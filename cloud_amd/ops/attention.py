@@ -1,14 +1,15 @@
 """Fused multi-head self-attention (K13) over a packed QKV projection.
 
-``attention(qkv, num_heads, key_len)`` computes, per batch entry and head,
-``softmax(Q K^T * scale + key mask) (dropout) V`` for ``qkv: [B, S, 3*H*D]`` packed
+``attention(qkv, num_heads, key_len, causal=...)`` computes, per batch entry and head,
+``softmax(Q K^T * scale + key mask [+ causal mask]) (dropout) V`` for ``qkv: [B, S, 3*H*D]`` packed
 ``Q | K | V`` with head ``h`` at columns ``h*D`` of each third -- the layout the QKV
 projection produces and the kernels of ``csrc/kernels/attn.hip`` read in place.  The
 result is ``[B, S, H*D]``.
 
 On MI355X (contiguous bf16 CUDA tensors, ``D == 64``) forward and backward run on the
 gfx950 MFMA kernels at any sequence length (S = 64 / 128 on the one-workgroup kernels);
-the backward recomputes the probabilities from the saved log-sum-exp and regenerates the
+with ``causal=True`` they skip the 64x64 score blocks that lie entirely in the future.  The
+backward recomputes the probabilities from the saved log-sum-exp and regenerates the
 dropout mask from the saved seed.  CPU tensors, other dtypes and other head dimensions run
 the same math in fp32 PyTorch.
 """
@@ -25,24 +26,24 @@ from .dropout import next_seed
 
 class _AttentionFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, qkv, key_len, H, scale, p, seed):
+    def forward(ctx, qkv, key_len, H, scale, p, seed, causal):
         B, S, _ = qkv.shape
         q2 = qkv.view(B * S, -1)
-        out, lse = raw.attn_fwd(q2, B, S, H, key_len, p, seed, scale=scale)
+        out, lse = raw.attn_fwd(q2, B, S, H, key_len, p, seed, scale=scale, causal=causal)
         ctx.save_for_backward(q2, out, lse, key_len)
-        ctx.cfg = (B, S, H, scale, p, seed)
+        ctx.cfg = (B, S, H, scale, p, seed, causal)
         return out.view(B, S, -1)
 
     @staticmethod
     def backward(ctx, dout):
         q2, out, lse, key_len = ctx.saved_tensors
-        B, S, H, scale, p, seed = ctx.cfg
+        B, S, H, scale, p, seed, causal = ctx.cfg
         dout = dout.contiguous().view(B * S, -1)
-        dqkv = raw.attn_bwd(q2, out, dout, lse, B, S, H, key_len, p, seed, scale=scale)
-        return dqkv.view(B, S, -1), None, None, None, None, None
+        dqkv = raw.attn_bwd(q2, out, dout, lse, B, S, H, key_len, p, seed, scale=scale, causal=causal)
+        return dqkv.view(B, S, -1), None, None, None, None, None, None
 
 
-def _reference(qkv, H, key_len, scale, p):
+def _reference(qkv, H, key_len, scale, p, causal=False):
     B, S, C3 = qkv.shape
     D = C3 // (3 * H)
     ct = torch.float64 if qkv.dtype == torch.float64 else torch.float32
@@ -52,17 +53,22 @@ def _reference(qkv, H, key_len, scale, p):
         kl = key_len.to(device=qkv.device, dtype=torch.long).clamp(1, S)
         pad = torch.arange(S, device=qkv.device)[None, :] >= kl[:, None]
         att = att.masked_fill(pad[:, None, None, :], float("-inf"))
+    if causal:
+        future = torch.ones(S, S, dtype=torch.bool, device=qkv.device).triu(1)  # [q, key]: key > q
+        att = att.masked_fill(future, float("-inf"))
     att = att.softmax(-1)
     if p > 0:
         att = F.dropout(att, p, training=True)
     return (att @ v).permute(0, 2, 1, 3).reshape(B, S, H * D).to(qkv.dtype)
 
 
-def attention(qkv, num_heads, key_len=None, dropout_p=0.0, training=True, scale=None, seed=None):
+def attention(qkv, num_heads, key_len=None, dropout_p=0.0, training=True, scale=None, seed=None, causal=False):
     """Multi-head self-attention of a packed projection ``qkv [B, S, 3*H*D]`` -> ``[B, S, H*D]``.
 
     ``key_len``: int tensor ``[B]``, the number of valid (leading) keys of each batch entry,
-    clamped to ``[1, S]``; ``None`` = all keys.  ``scale`` defaults to ``1 / sqrt(D)``.
+    clamped to ``[1, S]``; ``None`` = all keys.  ``causal``: query ``i`` sees key ``j`` only if
+    ``j <= i`` (and ``j < key_len``); key 0 is visible to every query, so no row is fully masked.
+    ``scale`` defaults to ``1 / sqrt(D)``.
     Dropout acts on the attention probabilities, only when ``training``; ``seed`` (an int)
     fixes the mask of the native path and defaults to ``ops.dropout.next_seed()``.
 
@@ -80,5 +86,5 @@ def attention(qkv, num_heads, key_len=None, dropout_p=0.0, training=True, scale=
         kl = None if key_len is None else key_len.to(device=qkv.device, dtype=torch.int32).contiguous()
         if p > 0 and seed is None:
             seed = next_seed()
-        return _AttentionFn.apply(qkv, kl, num_heads, scale, p, int(seed) if p > 0 else 0)
-    return _reference(qkv, num_heads, key_len, scale, p)
+        return _AttentionFn.apply(qkv, kl, num_heads, scale, p, int(seed) if p > 0 else 0, bool(causal))
+    return _reference(qkv, num_heads, key_len, scale, p, bool(causal))

@@ -887,26 +887,27 @@ def embed_bwd(dh, ids, tts, dword, dpos, dtype_, seq_len, n_types, pos_offset=0,
                                "(CLOUD_AMD_DETERMINISTIC=1)" % (C, n_types))
 
 
-def attn_fwd(qkv, B, S, H, key_len=None, p_drop=0.0, seed=0, scale=None):
+def attn_fwd(qkv, B, S, H, key_len=None, p_drop=0.0, seed=0, scale=None, causal=False):
     """qkv [B*S, 3*H*64] -> (ctx [B*S, H*64], lse [B, H, S]).  Any S; S = 64 / 128 take the
-    one-workgroup kernels."""
+    one-workgroup kernels.  ``causal``: key j is visible to query i iff j <= i (and j < key_len)."""
     ext = _ext.load(required=True)
     C = H * 64
     ctx = torch.empty((B * S, C), dtype=torch.bfloat16, device=qkv.device)
     lse = torch.empty((B, H, S), dtype=torch.float32, device=qkv.device)
     scale = 1.0 / 8.0 if scale is None else scale
     ext.attn_fwd(qkv.data_ptr(), ctx.data_ptr(), lse.data_ptr(), _ext.ptr(key_len), B, S, H, float(scale),
-                 float(p_drop), int(seed), _st(qkv.device))
+                 float(p_drop), int(seed), bool(causal), _st(qkv.device))
     return ctx, lse
 
 
-def attn_bwd(qkv, ctx, dctx, lse, B, S, H, key_len=None, p_drop=0.0, seed=0, scale=None):
+def attn_bwd(qkv, ctx, dctx, lse, B, S, H, key_len=None, p_drop=0.0, seed=0, scale=None, causal=False):
     ext = _ext.load(required=True)
     dqkv = torch.empty_like(qkv)
     dvec = torch.empty_like(lse)
     scale = 1.0 / 8.0 if scale is None else scale
     ext.attn_bwd(qkv.data_ptr(), ctx.data_ptr(), dctx.data_ptr(), lse.data_ptr(), dvec.data_ptr(), dqkv.data_ptr(),
-                 _ext.ptr(key_len), B, S, H, float(scale), float(p_drop), int(seed), _st(qkv.device))
+                 _ext.ptr(key_len), B, S, H, float(scale), float(p_drop), int(seed), bool(causal),
+                 _st(qkv.device))
     return dqkv
 
 

@@ -121,9 +121,9 @@ int ca_embed_bwd(const bf16_t*, const int32_t*, const int32_t*, float*, float*, 
                  int, float*, unsigned*, hipStream_t);
 int ca_dropout(const bf16_t*, bf16_t*, long, float, uint64_t, hipStream_t);
 int ca_dropout_mask(uint8_t*, long, long, float, uint64_t, hipStream_t);
-int ca_attn_fwd(const bf16_t*, bf16_t*, float*, const int*, int, int, int, float, float, uint64_t, hipStream_t);
+int ca_attn_fwd(const bf16_t*, bf16_t*, float*, const int*, int, int, int, float, float, uint64_t, int, hipStream_t);
 int ca_attn_bwd(const bf16_t*, const bf16_t*, const bf16_t*, const float*, float*, bf16_t*, const int*, int, int, int,
-                float, float, uint64_t, hipStream_t);
+                float, float, uint64_t, int, hipStream_t);
 }
 
 #define P(T, x) reinterpret_cast<T>(static_cast<uintptr_t>(x))
@@ -503,14 +503,15 @@ PYBIND11_MODULE(_C, m) {
     check(ca_dropout_mask(P(uint8_t*, m_), n, base, p, seed, S(s)), "dropout_mask");
   });
   m.def("attn_fwd", [](u64 qkv, u64 ctx, u64 lse, u64 klen, int B, int S_, int H, float scale, float p, u64 seed,
-                       u64 s) {
+                       bool causal, u64 s) {
     check(ca_attn_fwd(P(const bf16_t*, qkv), P(bf16_t*, ctx), P(float*, lse), P(const int*, klen), B, S_, H, scale, p,
-                      seed, S(s)), "attn_fwd");
+                      seed, causal ? 1 : 0, S(s)), "attn_fwd");
   });
   m.def("attn_bwd", [](u64 qkv, u64 out, u64 dout, u64 lse, u64 dvec, u64 dqkv, u64 klen, int B, int S_, int H,
-                       float scale, float p, u64 seed, u64 s) {
+                       float scale, float p, u64 seed, bool causal, u64 s) {
     check(ca_attn_bwd(P(const bf16_t*, qkv), P(const bf16_t*, out), P(const bf16_t*, dout), P(const float*, lse),
-                      P(float*, dvec), P(bf16_t*, dqkv), P(const int*, klen), B, S_, H, scale, p, seed, S(s)),
+                      P(float*, dvec), P(bf16_t*, dqkv), P(const int*, klen), B, S_, H, scale, p, seed,
+                      causal ? 1 : 0, S(s)),
           "attn_bwd");
   });
 }

@@ -24,6 +24,17 @@
 // masks: fragment rows >= S are clamped to row S - 1, tile rows >= S are zero-filled in LDS,
 // lse / Dv of queries >= S are not read (dKV: p = dS = 0 for those columns), and only rows
 // < S are stored.  The non-tail instantiation is the code that ran before the split.
+//
+// Causal mode (CAUSAL, a compile-time parameter of all six kernels; the non-causal
+// instantiations are the code without it): key j is visible to query i iff j <= i and
+// j < key_len[b], so key 0 is visible to every query and no row is fully masked.  The generic
+// kernels skip the 64x64 blocks that lie entirely in the future -- forward and dQ stop after the
+// diagonal key block, dK/dV starts at the diagonal query block, all bounds workgroup-uniform --
+// and test key <= q per element in the diagonal block only.  The one-workgroup kernels mask per
+// element; the forward one also skips the MFMA steps that are entirely in the future of a wave's
+// rows, the fused backward does not (at S = 128 it sits at its 128-register budget, and every
+// wave-dependent skip tried there spilled).  A masked element is exactly p = 0, dS = 0.  The
+// dropout element index is the same in both modes.
 #include "ca_mfma_core.h"
 #include "ca_rng.h"
 
@@ -97,6 +108,24 @@ __device__ __forceinline__ float grp16_sum(float v) {
   return v;
 }
 
+// The 64-row block of a workgroup of the generic kernels.  Causal work per workgroup grows
+// (forward, dQ) or shrinks (dK/dV) with the block index, and the hardware hands consecutive
+// workgroup ids to its XCDs and their shader engines round-robin: whenever gridDim.x divides that
+// period, the same engine gets the longest block of every (batch, head), and the causal launch
+// takes as long as the full one (measured: 1.00 x at S = 256 .. 2048).  So the block index is
+// rotated by a multiplicative hash of the (batch, head) index: every engine then gets a random
+// mix of lengths, whatever the period and gridDim.x (a plain rotation by the index still leaves
+// gridDim.x = 2 and 4 at 1.00 x in a model of 32 round-robin engines; the hash stays within
+// 0.03 of (n + 1) / 2n for n = 2 .. 32).  Workgroup-uniform.
+template <bool CAUSAL>
+__device__ __forceinline__ int block_x() {
+  if constexpr (CAUSAL) {
+    const uint32_t rot = ((blockIdx.y + gridDim.y * blockIdx.z) * 0x9E3779B1u) >> 16;
+    return (int)((blockIdx.x + rot) % gridDim.x);
+  }
+  return (int)blockIdx.x;
+}
+
 struct AttnArgs {
   const bf16_t* qkv;   // [B*S][3*H*D]
   const bf16_t* out;   // ctx [B*S][H*D] (bwd: O)
@@ -111,16 +140,17 @@ struct AttnArgs {
   DropCfg drop;
 };
 
-template <bool TAIL>
+template <bool TAIL, bool CAUSAL>
 __global__ void __launch_bounds__(256) attn_fwd_kernel(AttnArgs a) {
   __shared__ __attribute__((aligned(16))) short Ks[KB * LDT];
   __shared__ __attribute__((aligned(16))) short Vs[KB * LDT];
   __shared__ __attribute__((aligned(16))) short Ps[4][16 * PLD];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int b = blockIdx.z, h = blockIdx.y;
+  const int bx = block_x<CAUSAL>();
   const int S = a.S, H = a.H, C = H * D;
   const long ldq = 3L * C;
-  const int q0 = blockIdx.x * QB + wave * 16;
+  const int q0 = bx * QB + wave * 16;
   int klen = a.key_len ? a.key_len[b] : S;
   klen = klen < 1 ? 1 : (klen > S ? S : klen);
   const bf16_t* base = a.qkv + (long)b * S * ldq;
@@ -131,22 +161,31 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(AttnArgs a) {
   const uint64_t bhss = (uint64_t)bh * S * S;  // dropout index of element (q, key): bhss + q*S + key
 
   f4v o[4];
-  float m[4], l[4];
+  // causal: lr = the row sum of the probabilities as the P V product sees them (rounded to bf16).
+  // The context is divided by lr, so its weights sum to one exactly; the log-sum-exp keeps the
+  // unrounded sum l, which is what the backward recomputes P from.  A causal row has as few as one
+  // or two visible keys, where dS = P (dP - Dv) nearly cancels and Dv = rowsum(dO * ctx) must not
+  // carry the weights' rounding as an absolute error: dividing by l left 2.0e-2 on a dK block at
+  // S = 2 where dividing by lr leaves 7.6e-3.  The non-causal kernels divide by l as before.
+  float m[4], l[4], lr[4];
 #pragma unroll
   for (int t = 0; t < 4; ++t) o[t] = f4v{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     m[r] = -INFINITY;
-    l[r] = 0.f;
+    l[r] = lr[r] = 0.f;
   }
   short* slab = Ps[wave];
-  const int nkb = (klen + KB - 1) / KB;
+  int nkb = (klen + KB - 1) / KB;
+  // causal: key blocks past the diagonal one (QB == KB) are entirely in the future
+  if constexpr (CAUSAL) nkb = nkb < bx + 1 ? nkb : bx + 1;
   for (int kb = 0; kb < nkb; ++kb) {
     const int k0 = kb * KB;
     __syncthreads();
     tile_load<TAIL>(Ks, base + (long)k0 * ldq + C + h * D, ldq, tid, S - k0);
     tile_load<TAIL>(Vs, base + (long)k0 * ldq + 2 * C + h * D, ldq, tid, S - k0);
     __syncthreads();
+    const bool diag = CAUSAL && kb == bx;  // the only block that needs key <= q
     f4v s[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
@@ -158,10 +197,15 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(AttnArgs a) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       float mx = -INFINITY;
+      int kend = klen;  // first masked key of this row
+      if constexpr (CAUSAL) {
+        const int q = q0 + (lane >> 4) * 4 + r;
+        kend = (diag && q + 1 < klen) ? q + 1 : klen;
+      }
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
         const int key = k0 + t * 16 + (lane & 15);
-        const float v = key < klen ? s[t][r] * c2 : -INFINITY;
+        const float v = key < kend ? s[t][r] * c2 : -INFINITY;
         s[t][r] = v;
         mx = fmaxf(mx, v);
       }
@@ -169,14 +213,16 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(AttnArgs a) {
       const float mn = fmaxf(m[r], mx);
       alpha[r] = exp2f(m[r] - mn);
       m[r] = mn;
-      float ls = 0.f;
+      float ls = 0.f, lsr = 0.f;
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
         const float p = exp2f(s[t][r] - mn);
         ls += p;
+        if constexpr (CAUSAL) lsr += bf2f(f2bf(p));
         s[t][r] = p;
       }
       l[r] = l[r] * alpha[r] + ls;
+      if constexpr (CAUSAL) lr[r] = lr[r] * alpha[r] + lsr;
     }
     if (a.drop.on) {
 #pragma unroll
@@ -206,7 +252,7 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(AttnArgs a) {
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const float lt = grp16_sum(l[r]);
-    inv[r] = 1.f / lt;
+    inv[r] = 1.f / (CAUSAL ? grp16_sum(lr[r]) : lt);
     if ((lane & 15) == 0 && (!TAIL || q0 + (lane >> 4) * 4 + r < S))
       a.lse[bh * S + q0 + (lane >> 4) * 4 + r] = m[r] + log2f(lt);
   }
@@ -251,7 +297,7 @@ __global__ void __launch_bounds__(256) attn_bwd_prep_kernel(AttnArgs a) {
   }
 }
 
-template <bool TAIL>
+template <bool TAIL, bool CAUSAL>
 __global__ void __launch_bounds__(256) attn_bwd_dkv_kernel(AttnArgs a) {
   __shared__ __attribute__((aligned(16))) short Qs[QB * LDT];
   __shared__ __attribute__((aligned(16))) short Gs[QB * LDT];  // dO
@@ -260,9 +306,10 @@ __global__ void __launch_bounds__(256) attn_bwd_dkv_kernel(AttnArgs a) {
   __shared__ float lse_s[QB], dv_s[QB];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int b = blockIdx.z, h = blockIdx.y;
+  const int bx = block_x<CAUSAL>();
   const int S = a.S, H = a.H, C = H * D;
   const long ldq = 3L * C;
-  const int k0 = blockIdx.x * KB + wave * 16;  // this wave's 16 keys
+  const int k0 = bx * KB + wave * 16;  // this wave's 16 keys
   int klen = a.key_len ? a.key_len[b] : S;
   klen = klen < 1 ? 1 : (klen > S ? S : klen);
   const long bh = (long)b * H + h;
@@ -279,10 +326,12 @@ __global__ void __launch_bounds__(256) attn_bwd_dkv_kernel(AttnArgs a) {
   for (int t = 0; t < 4; ++t) dk[t] = dv[t] = f4v{0.f, 0.f, 0.f, 0.f};
   short* pslab = Ps[wave];
   short* dslab = Ds[wave];
-  const bool any_valid = blockIdx.x * KB < klen;
+  const bool any_valid = (uint32_t)bx * KB < (uint32_t)klen;
   const int nqb = any_valid ? (TAIL ? (S + QB - 1) / QB : S / QB) : 0;
-  for (int qb = 0; qb < nqb; ++qb) {
+  // causal: query blocks before the diagonal one (QB == KB) see none of this block's keys
+  for (int qb = CAUSAL ? bx : 0; qb < nqb; ++qb) {
     const int q0 = qb * QB;
+    const bool diag = CAUSAL && qb == bx;  // the only block that needs key <= q
     __syncthreads();
     tile_load<TAIL>(Qs, base + (long)q0 * ldq + h * D, ldq, tid, S - q0);
     tile_load<TAIL>(Gs, a.dout + ((long)b * S + q0) * C + h * D, C, tid, S - q0);
@@ -309,10 +358,12 @@ __global__ void __launch_bounds__(256) attn_bwd_dkv_kernel(AttnArgs a) {
       const int qi = t * 16 + (lane & 15);
       const float ls = lse_s[qi], dvq = dv_s[qi];
       const bool qlive = !TAIL || q0 + qi < S;  // a query column >= S adds p = dS = 0
+      int kend = klen;  // first masked key of this query column
+      if constexpr (CAUSAL) kend = (diag && q0 + qi + 1 < klen) ? q0 + qi + 1 : klen;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int key = k0 + (lane >> 4) * 4 + r;
-        const float pr = (key < klen && qlive) ? exp2f(p[t][r] * c2 - ls) : 0.f;
+        const float pr = (key < kend && qlive) ? exp2f(p[t][r] * c2 - ls) : 0.f;
         const float mul = a.drop.on ? drop_mul(a.drop, bhss + (uint32_t)((q0 + qi) * S + key)) : 1.f;
         pd[t][r] = pr * mul;
         ds[t][r] = pr * (dp[t][r] * mul - dvq);
@@ -356,17 +407,21 @@ __global__ void __launch_bounds__(256) attn_bwd_dkv_kernel(AttnArgs a) {
 
 // (the tail variant's few extra index registers would cost the third wave per SIMD that the
 // non-tail one gets unasked: 174 against 168 registers; "1" is the default)
-template <bool TAIL>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TAIL ? 3 : 1)))
+// Causal, non-tail: the diagonal test takes it to 141 + 32 = 173 registers and two waves when left
+// alone; asked for three it fits in 160 without scratch, like the tail variants (154).
+#define DQ_WAVES(TAIL, CAUSAL) (((TAIL) || (CAUSAL)) ? 3 : 1)
+template <bool TAIL, bool CAUSAL>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DQ_WAVES(TAIL, CAUSAL))))
 attn_bwd_dq_kernel(AttnArgs a) {
   __shared__ __attribute__((aligned(16))) short Ks[KB * LDT];
   __shared__ __attribute__((aligned(16))) short Vs[KB * LDT];
   __shared__ __attribute__((aligned(16))) short Ds[4][16 * PLD];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int b = blockIdx.z, h = blockIdx.y;
+  const int bx = block_x<CAUSAL>();
   const int S = a.S, H = a.H, C = H * D;
   const long ldq = 3L * C;
-  const int q0 = blockIdx.x * QB + wave * 16;
+  const int q0 = bx * QB + wave * 16;
   int klen = a.key_len ? a.key_len[b] : S;
   klen = klen < 1 ? 1 : (klen > S ? S : klen);
   const long bh = (long)b * H + h;
@@ -389,13 +444,16 @@ attn_bwd_dq_kernel(AttnArgs a) {
 #pragma unroll
   for (int t = 0; t < 4; ++t) dq[t] = f4v{0.f, 0.f, 0.f, 0.f};
   short* dslab = Ds[wave];
-  const int nkb = (klen + KB - 1) / KB;
+  int nkb = (klen + KB - 1) / KB;
+  // causal: key blocks past the diagonal one (QB == KB) are entirely in the future
+  if constexpr (CAUSAL) nkb = nkb < bx + 1 ? nkb : bx + 1;
   for (int kb = 0; kb < nkb; ++kb) {
     const int k0 = kb * KB;
     __syncthreads();
     tile_load<TAIL>(Ks, base + (long)k0 * ldq + C + h * D, ldq, tid, S - k0);
     tile_load<TAIL>(Vs, base + (long)k0 * ldq + 2 * C + h * D, ldq, tid, S - k0);
     __syncthreads();
+    const bool diag = CAUSAL && kb == bx;  // the only block that needs key <= q
     f4v s[4], dp[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
@@ -412,7 +470,9 @@ attn_bwd_dq_kernel(AttnArgs a) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int q = q0 + (lane >> 4) * 4 + r;
-        const float pr = key < klen ? exp2f(s[t][r] * c2 - ls[r]) : 0.f;
+        bool vis = key < klen;
+        if constexpr (CAUSAL) vis = vis && (!diag || key <= q);
+        const float pr = vis ? exp2f(s[t][r] * c2 - ls[r]) : 0.f;
         const float mul = a.drop.on ? drop_mul(a.drop, bhss + (uint32_t)(q * S + key)) : 1.f;
         s[t][r] = pr * (dp[t][r] * mul - dvq[r]);
       }
@@ -488,7 +548,7 @@ __device__ __forceinline__ void stage_store(short* slab, const f4v (&v)[4], bf16
   }
 }
 
-template <int SQ>
+template <int SQ, bool CAUSAL>
 __global__ void __launch_bounds__(SQ * 4) __attribute__((amdgpu_waves_per_eu(4))) attn_bwd_fused_kernel(AttnArgs a) {
   constexpr int NW = SQ / 16, NT = NW * 64, TQ = SQ / 16, PL = SQ + 8, LCH = SQ * 8 / NT;
   // Qs: Q; Gs: dO (phase A), then K (phase B); Xs [q][key]: each wave's P columns, then
@@ -551,17 +611,22 @@ __global__ void __launch_bounds__(SQ * 4) __attribute__((amdgpu_waves_per_eu(4))
     }
     // p[t][r] = S^T[key = k0 + 4 (l >> 4) + r][q = 16 t + (l & 15)]
     const int kr = k0 + (lane >> 4) * 4;
+    const int cdiag = (lane & 15) + 1 - kr;  // causal: qi + 1 - kr at t = 0
 #pragma unroll
     for (int t = 0; t < TQ; ++t) {
       const int qi = t * 16 + (lane & 15);
       const float ls = lse_s[qi], dvq = dv_s[qi];
       s4v pk;
+      // causal: keys kr + r, r < nvis, are visible to this query column (kr + r < klen and kr + r <= qi);
+      // one count per column, because a second per-element test spilled at S = 128
+      int nvis = klen - kr;
+      if constexpr (CAUSAL) nvis = nvis < cdiag + t * 16 ? nvis : cdiag + t * 16;
       float dm[4] = {1.f, 1.f, 1.f, 1.f};  // the row's four consecutive keys: two hashes
       if (a.drop.on) drop_mul4(a.drop, bhss + (uint32_t)(qi * SQ + kr), dm);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int key = kr + r;
-        const float pr = key < klen ? exp2f(p[t][r] * c2 - ls) : 0.f;
+        const float pr = (CAUSAL ? r < nvis : key < klen) ? exp2f(p[t][r] * c2 - ls) : 0.f;
         const float mul = dm[r];
         pk[r] = (short)f2bf(pr * mul);
         dsr[t][r] = (short)f2bf(pr * (dp[t][r] * mul - dvq));
@@ -645,7 +710,7 @@ __global__ void __launch_bounds__(SQ * 4) __attribute__((amdgpu_waves_per_eu(4))
 // output tile in its own 16 rows of it -- three 8-wave blocks per CU (72 VGPRs), so the
 // B x H = 768 blocks of BERT-base b64 run in one round instead of 1.5 (per-wave P slabs
 // beside K / V took 72 KB: two blocks per CU).
-template <int SQ>
+template <int SQ, bool CAUSAL>
 __global__ void __launch_bounds__(SQ * 4) attn_fwd_short_kernel(AttnArgs a) {
   constexpr int NW = SQ / 16, NT = NW * 64, TK = SQ / 16;
   static_assert(NW * 16 == SQ, "one 16-row slab of the K image per wave");
@@ -679,29 +744,39 @@ __global__ void __launch_bounds__(SQ * 4) attn_fwd_short_kernel(AttnArgs a) {
 #pragma unroll
   for (int t = 0; t < TK; ++t) {
     s[t] = f4v{0.f, 0.f, 0.f, 0.f};
+    if (CAUSAL && t > wave) continue;  // keys 16 t .. 16 t + 15 all follow this wave's queries: masked below
     s[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf0, frag_kc<LDT>(Ks, t * 16, 0, lane), s[t], 0, 0, 0);
     s[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf1, frag_kc<LDT>(Ks, t * 16, 32, lane), s[t], 0, 0, 0);
   }
-  float m[4], l[4];
+  // causal: lr = the row sum of the probabilities as the P V product sees them (rounded to bf16);
+  // the context is normalised by it, the log-sum-exp keeps the unrounded sum (see attn_fwd_kernel)
+  float m[4], l[4], lr[4];
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     float mx = -INFINITY;
+    int kend = klen;  // first masked key of this row
+    if constexpr (CAUSAL) {
+      const int q = q0 + (lane >> 4) * 4 + r;
+      kend = q + 1 < klen ? q + 1 : klen;
+    }
 #pragma unroll
     for (int t = 0; t < TK; ++t) {
       const int key = t * 16 + (lane & 15);
-      const float v = key < klen ? s[t][r] * c2 : -INFINITY;
+      const float v = key < kend ? s[t][r] * c2 : -INFINITY;
       s[t][r] = v;
       mx = fmaxf(mx, v);
     }
     m[r] = grp16_max(mx);
-    float ls = 0.f;
+    float ls = 0.f, lsr = 0.f;
 #pragma unroll
     for (int t = 0; t < TK; ++t) {
       const float p = exp2f(s[t][r] - m[r]);
       ls += p;
+      if constexpr (CAUSAL) lsr += bf2f(f2bf(p));
       s[t][r] = p;
     }
     l[r] = grp16_sum(ls);
+    if constexpr (CAUSAL) lr[r] = grp16_sum(lsr);
   }
   // every wave's QK^T reads of Ks are done past this barrier: its rows become P slabs
   __syncthreads();
@@ -711,6 +786,7 @@ __global__ void __launch_bounds__(SQ * 4) attn_fwd_short_kernel(AttnArgs a) {
   for (int t = 0; t < 4; ++t) o[t] = f4v{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int half = 0; half < SQ / 64; ++half) {
+    if (CAUSAL && half * 64 > q0 + 15) continue;  // P is zero for these 64 keys
     if (half) __builtin_amdgcn_wave_barrier();  // the previous half's P reads precede these writes
 #pragma unroll
     for (int tt = 0; tt < 4; ++tt) {
@@ -742,7 +818,7 @@ __global__ void __launch_bounds__(SQ * 4) attn_fwd_short_kernel(AttnArgs a) {
   }
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    const float inv = 1.f / l[r];
+    const float inv = 1.f / (CAUSAL ? lr[r] : l[r]);
     if ((lane & 15) == 0) a.lse[(long)bh * SQ + q0 + (lane >> 4) * 4 + r] = m[r] + log2f(l[r]);
 #pragma unroll
     for (int t = 0; t < 4; ++t) o[t][r] *= inv;
@@ -752,6 +828,36 @@ __global__ void __launch_bounds__(SQ * 4) attn_fwd_short_kernel(AttnArgs a) {
 }
 
 bool shape_ok(int S, int H) { return S > 0 && H > 0; }
+
+static_assert(QB == KB, "one grid for the key-block and the query-block kernels; causal diagonal block = own block");
+dim3 block_grid(const AttnArgs& a) { return dim3((a.S + QB - 1) / QB, a.H, a.B); }
+
+template <bool CAUSAL>
+void launch_fwd(const AttnArgs& a, hipStream_t s) {
+  if (a.S % QB) attn_fwd_kernel<true, CAUSAL><<<block_grid(a), 256, 0, s>>>(a);
+  else attn_fwd_kernel<false, CAUSAL><<<block_grid(a), 256, 0, s>>>(a);
+}
+template <bool CAUSAL>
+void launch_bwd_dkv(const AttnArgs& a, hipStream_t s) {
+  if (a.S % QB) attn_bwd_dkv_kernel<true, CAUSAL><<<block_grid(a), 256, 0, s>>>(a);
+  else attn_bwd_dkv_kernel<false, CAUSAL><<<block_grid(a), 256, 0, s>>>(a);
+}
+template <bool CAUSAL>
+void launch_bwd_dq(const AttnArgs& a, hipStream_t s) {
+  if (a.S % QB) attn_bwd_dq_kernel<true, CAUSAL><<<block_grid(a), 256, 0, s>>>(a);
+  else attn_bwd_dq_kernel<false, CAUSAL><<<block_grid(a), 256, 0, s>>>(a);
+}
+// S = 64 / 128 only
+template <bool CAUSAL>
+void launch_fwd_short(const AttnArgs& a, hipStream_t s) {
+  if (a.S == 128) attn_fwd_short_kernel<128, CAUSAL><<<a.B * a.H, 512, 0, s>>>(a);
+  else attn_fwd_short_kernel<64, CAUSAL><<<a.B * a.H, 256, 0, s>>>(a);
+}
+template <bool CAUSAL>
+void launch_bwd_fused(const AttnArgs& a, hipStream_t s) {
+  if (a.S == 128) attn_bwd_fused_kernel<128, CAUSAL><<<a.B * a.H, 512, 0, s>>>(a);
+  else attn_bwd_fused_kernel<64, CAUSAL><<<a.B * a.H, 256, 0, s>>>(a);
+}
 
 // CLOUD_AMD_ATTN_FUSED_BWD=0 keeps the three-kernel backward at S <= 128 (A/B runs)
 bool fused_bwd_enabled() {
@@ -768,21 +874,21 @@ bool fused_bwd_enabled() {
 extern "C" {
 
 // ctx = softmax(Q K^T * scale + keymask) (dropout) V ; lse[B][H][S] saved for the backward.
+// causal != 0: key j is visible to query i iff j <= i (and j < key_len[b]).
 int ca_attn_fwd(const bf16_t* qkv, bf16_t* ctx, float* lse, const int* key_len, int B, int S, int H, float scale,
-                float p_drop, uint64_t seed, hipStream_t s) {
+                float p_drop, uint64_t seed, int causal, hipStream_t s) {
   if (!shape_ok(S, H)) return -1;
   AttnArgs a{};
   a.qkv = qkv; a.ctx = ctx; a.lse = lse; a.key_len = key_len;
   a.B = B; a.S = S; a.H = H; a.scale = scale; a.drop = make_drop(p_drop, seed);
   if ((S == 64 || S == 128) && fused_bwd_enabled()) {
-    if (S == 128) attn_fwd_short_kernel<128><<<B * H, 512, 0, s>>>(a);
-    else attn_fwd_short_kernel<64><<<B * H, 256, 0, s>>>(a);
+    if (causal) launch_fwd_short<true>(a, s);
+    else launch_fwd_short<false>(a, s);
     CA_LAUNCH_CHECK();
     return 0;
   }
-  const dim3 grid((S + QB - 1) / QB, H, B);
-  if (S % QB) attn_fwd_kernel<true><<<grid, 256, 0, s>>>(a);
-  else attn_fwd_kernel<false><<<grid, 256, 0, s>>>(a);
+  if (causal) launch_fwd<true>(a, s);
+  else launch_fwd<false>(a, s);
   CA_LAUNCH_CHECK();
   return 0;
 }
@@ -790,27 +896,25 @@ int ca_attn_fwd(const bf16_t* qkv, bf16_t* ctx, float* lse, const int* key_len, 
 // dqkv (all three thirds written) from dctx; dvec: [B][H][S] fp32 scratch.
 int ca_attn_bwd(const bf16_t* qkv, const bf16_t* out, const bf16_t* dout, const float* lse, float* dvec,
                 bf16_t* dqkv, const int* key_len, int B, int S, int H, float scale, float p_drop, uint64_t seed,
-                hipStream_t s) {
+                int causal, hipStream_t s) {
   if (!shape_ok(S, H)) return -1;
   AttnArgs a{};
   a.qkv = qkv; a.out = out; a.dout = dout; a.lse = const_cast<float*>(lse); a.dvec = dvec; a.dqkv = dqkv;
   a.key_len = key_len; a.B = B; a.S = S; a.H = H; a.scale = scale; a.drop = make_drop(p_drop, seed);
   if ((S == 64 || S == 128) && fused_bwd_enabled()) {
-    if (S == 128) attn_bwd_fused_kernel<128><<<B * H, 512, 0, s>>>(a);
-    else attn_bwd_fused_kernel<64><<<B * H, 256, 0, s>>>(a);
+    if (causal) launch_bwd_fused<true>(a, s);
+    else launch_bwd_fused<false>(a, s);
     CA_LAUNCH_CHECK();
     return 0;
   }
   const long rows = (long)B * S * H;
   attn_bwd_prep_kernel<<<ca_cdiv(rows, 32), 256, 0, s>>>(a);
   CA_LAUNCH_CHECK();
-  static_assert(QB == KB, "one grid for the key-block and the query-block kernels");
-  const dim3 grid((S + QB - 1) / QB, H, B);
-  if (S % QB) attn_bwd_dkv_kernel<true><<<grid, 256, 0, s>>>(a);
-  else attn_bwd_dkv_kernel<false><<<grid, 256, 0, s>>>(a);
+  if (causal) launch_bwd_dkv<true>(a, s);
+  else launch_bwd_dkv<false>(a, s);
   CA_LAUNCH_CHECK();
-  if (S % QB) attn_bwd_dq_kernel<true><<<grid, 256, 0, s>>>(a);
-  else attn_bwd_dq_kernel<false><<<grid, 256, 0, s>>>(a);
+  if (causal) launch_bwd_dq<true>(a, s);
+  else launch_bwd_dq<false>(a, s);
   CA_LAUNCH_CHECK();
   return 0;
 }
