@@ -177,7 +177,10 @@ __global__ void __launch_bounds__(256) gmp_fwd_kernel(const bf16_t* __restrict__
   }
 }
 
-// dx = (x == y) * dy / cnt, written for every input element (no separate zero fill)
+// dx = (x == y) * dy / cnt, written for every input element (no separate zero fill).  The compare
+// is on VALUES, as the forward's tie count is: +0.0 and -0.0 are one maximum, so a channel that
+// holds both shares dy over all of them (a compare of the bf16 bit patterns gave the gradient only
+// to the zeros with the sign of the first one seen, and the shares no longer summed to dy).
 template <typename TI>
 __global__ void __launch_bounds__(256) gmp_bwd_kernel(const TI* __restrict__ dy, const bf16_t* __restrict__ x,
                                                       const bf16_t* __restrict__ y, const float* __restrict__ cnt,
@@ -197,7 +200,7 @@ __global__ void __launch_bounds__(256) gmp_bwd_kernel(const TI* __restrict__ dy,
       float g;
       if constexpr (sizeof(TI) == 2) g = bf2f(dy[i]);
       else g = dy[i];
-      o[j] = xv[j] == yv[j] ? f2bf(g / cnt[i]) : (bf16_t)0;
+      o[j] = bf2f(xv[j]) == bf2f(yv[j]) ? f2bf(g / cnt[i]) : (bf16_t)0;
     }
     *reinterpret_cast<us8*>(dx + r * C + vc * 8) = o;
   }

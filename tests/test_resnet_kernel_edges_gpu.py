@@ -1,7 +1,9 @@
 """Geometry-edge reference tests for the ResNet-path kernels: the implicit-GEMM convolutions
 (conv.hip: forward, input gradient, split-K weight gradient, their BN-statistics epilogues), the
 LDS-resident 3x3 kernel (ca_conv_halo.h), the max-pools and the fused stem tail (pool.hip) and
-the BatchNorm statistics (bn.hip).
+the BatchNorm statistics with a large mean (bn.hip; everything else about the BatchNorm kernels
+and the global pools -- tiling branches, gates, backward, switches -- is in
+test_bn_kernel_edges_gpu.py, with its references in test_bn_reference_cpu.py).
 
 Every reference is computed in float64 on the host from the same bf16 operands the kernel reads;
 inputs come from a host ``torch.Generator``.  The shapes are the smallest that enter the loader
