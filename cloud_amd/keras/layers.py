@@ -378,8 +378,12 @@ class MultiHeadAttention(Layer):
     Self-attention (``query is value``, no ``key`` or the same tensor) without an
     ``attention_mask`` and without ``return_attention_scores`` is one packed projection,
     ``ops.attention`` and the output projection: under the mixed policy with ``key_dim == 64``
-    all three run on the in-tree kernels, forward and backward.  Everything else
-    (cross-attention, an explicit mask, returned scores) is the same math in PyTorch.
+    all three run on the in-tree kernels, forward and backward.  Cross-attention (``query`` is
+    not ``value``) without a mask, returned scores or the causal flag is native under the same
+    conditions: the Q projection from the first third of ``qkv_kernel``, the K | V projection
+    from the other two as one GEMM (two and a concatenation when ``key`` is a tensor of its own),
+    ``ops.cross_attention`` and the output projection.  Everything else (an explicit mask,
+    returned scores, causal cross-attention) is the same math in PyTorch.
 
     Calls: Keras style ``layer(query, value, key=None, attention_mask=None,
     use_causal_mask=False, return_attention_scores=False, training=None)``, or the list form
@@ -461,6 +465,17 @@ class MultiHeadAttention(Layer):
         if query is value and key is value and attention_mask is None and not return_attention_scores:
             qkv = dense_op(query.to(dt), self.qkv_kernel, self.qkv_bias, None)
             ctx = ops.attention(qkv, H, None, p, bool(training), causal=causal)
+            return dense_op(ctx, self.out_kernel, self.out_bias, None)
+        if attention_mask is None and not return_attention_scores and not causal:
+            bias = self.qkv_bias
+            q = dense_op(query.to(dt), self.qkv_kernel[:hd], None if bias is None else bias[:hd], None)
+            if key is value:  # K | V are adjacent row blocks of the packed kernel: one GEMM
+                kv = dense_op(value.to(dt), self.qkv_kernel[hd:], None if bias is None else bias[hd:], None)
+            else:
+                k = dense_op(key.to(dt), self.qkv_kernel[hd:2 * hd], None if bias is None else bias[hd:2 * hd], None)
+                v = dense_op(value.to(dt), self.qkv_kernel[2 * hd:], None if bias is None else bias[2 * hd:], None)
+                kv = torch.cat([k, v], dim=-1)
+            ctx = ops.cross_attention(q, kv, H, None, p, bool(training))
             return dense_op(ctx, self.out_kernel, self.out_bias, None)
 
         def proj(x, i):

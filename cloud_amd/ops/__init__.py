@@ -5,7 +5,7 @@ kernels in ``cloud_amd/_C*.so`` and CPU tensors to an fp32-faithful PyTorch
 reference (see :mod:`cloud_amd.ops._ext` for the fail-loudly policy).
 """
 from ._ext import load as load_extension, ops_mode, use_native  # noqa: F401
-from .attention import attention  # noqa: F401
+from .attention import attention, cross_attention  # noqa: F401
 from .batchnorm import bn_act  # noqa: F401
 from .conv import conv2d_nhwc  # noqa: F401
 from .gemm import linear  # noqa: F401

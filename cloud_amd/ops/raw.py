@@ -911,6 +911,55 @@ def attn_bwd(qkv, ctx, dctx, lse, B, S, H, key_len=None, p_drop=0.0, seed=0, sca
     return dqkv
 
 
+def _cross_operands(q, kv, B, T, S, H):
+    """The shape, pitch and alignment contract of the cross-attention kernels (16-byte loads)."""
+    C = H * 64
+    for name, t, shape in (("q", q, (B * T, C)), ("kv", kv, (B * S, 2 * C))):
+        if t.dtype != torch.bfloat16 or tuple(t.shape) != shape:
+            raise ValueError(f"attn_cross: {name} must be bf16 {shape}, got {t.dtype} {tuple(t.shape)}")
+        if t.stride(1) != 1 or t.stride(0) % 8 or t.stride(0) < 0:
+            raise ValueError(f"attn_cross: {name} needs unit column stride and a row pitch that is a multiple "
+                             f"of 8 elements, got strides {tuple(t.stride())}")
+        if t.data_ptr() % 16:
+            raise ValueError(f"attn_cross: {name} must start on a 16-byte boundary")
+    if B < 1 or T < 1 or S < 1 or H < 1 or T * S >= 2 ** 31:
+        raise ValueError(f"attn_cross: B, T, S, H must be >= 1 and T * S < 2^31, got {(B, T, S, H)}")
+
+
+def attn_cross_fwd(q, kv, B, T, S, H, key_len=None, p_drop=0.0, seed=0, scale=None):
+    """Cross-attention: q [B*T, H*64] and kv [B*S, 2*H*64] (K | V) -> (ctx [B*T, H*64], lse [B, H, T]).
+    Any T and S; both operands may be column slices of wider tensors (unit column stride, the
+    row pitch is ``stride(0)``).  ``key_len`` [B] int32: the number of valid leading keys, clamped
+    to [1, S].  The dropout element index is ``(b*H + h)*T*S + q*S + key``."""
+    ext = _ext.load(required=True)
+    _cross_operands(q, kv, B, T, S, H)
+    ctx = torch.empty((B * T, H * 64), dtype=torch.bfloat16, device=q.device)
+    lse = torch.empty((B, H, T), dtype=torch.float32, device=q.device)
+    scale = 1.0 / 8.0 if scale is None else scale
+    ext.attn_cross_fwd(q.data_ptr(), kv.data_ptr(), ctx.data_ptr(), lse.data_ptr(), _ext.ptr(key_len), B, T, S, H,
+                       q.stride(0), kv.stride(0), float(scale), float(p_drop), int(seed), _st(q.device))
+    return ctx, lse
+
+
+def attn_cross_bwd(q, kv, ctx, dctx, lse, B, T, S, H, key_len=None, p_drop=0.0, seed=0, scale=None):
+    """-> (dq [B*T, H*64], dkv [B*S, 2*H*64]), both contiguous; ``ctx`` and ``dctx`` are contiguous
+    [B*T, H*64].  dK / dV rows of keys >= key_len are zeros."""
+    ext = _ext.load(required=True)
+    _cross_operands(q, kv, B, T, S, H)
+    C = H * 64
+    for name, t in (("ctx", ctx), ("dctx", dctx)):
+        if t.dtype != torch.bfloat16 or tuple(t.shape) != (B * T, C) or not t.is_contiguous():
+            raise ValueError(f"attn_cross_bwd: {name} must be contiguous bf16 {(B * T, C)}")
+    dq = torch.empty((B * T, C), dtype=torch.bfloat16, device=q.device)
+    dkv = torch.empty((B * S, 2 * C), dtype=torch.bfloat16, device=q.device)
+    dvec = torch.empty_like(lse)
+    scale = 1.0 / 8.0 if scale is None else scale
+    ext.attn_cross_bwd(q.data_ptr(), kv.data_ptr(), ctx.data_ptr(), dctx.data_ptr(), lse.data_ptr(), dvec.data_ptr(),
+                       dq.data_ptr(), dkv.data_ptr(), _ext.ptr(key_len), B, T, S, H, q.stride(0), kv.stride(0),
+                       float(scale), float(p_drop), int(seed), _st(q.device))
+    return dq, dkv
+
+
 def dropout(x, p, seed, out=None):
     ext = _ext.load(required=True)
     y = out if out is not None else torch.empty_like(x)

@@ -35,6 +35,9 @@
 // rows, the fused backward does not (at S = 128 it sits at its 128-register budget, and every
 // wave-dependent skip tried there spilled).  A masked element is exactly p = 0, dS = 0.  The
 // dropout element index is the same in both modes.
+//
+// Cross-attention (queries and keys / values in separate tensors, own lengths and row pitches)
+// has three generic kernels of its own below the self-attention ones: see CrossArgs.
 #include "ca_mfma_core.h"
 #include "ca_rng.h"
 
@@ -504,6 +507,339 @@ attn_bwd_dq_kernel(AttnArgs a) {
 }
 
 // ---------------------------------------------------------------------------
+// Cross-attention: T queries q[B*T][H*D] (row pitch ldq) against S keys / values packed as
+// kv[B*S][2*H*D] (K | V, row pitch ldkv), T and S independent, non-causal.  The three kernels are
+// the non-causal generic ones above with the query rows and the key / value rows taken apart:
+// the same block loops, arithmetic and operation order, so with T == S, q = qkv[:, :C] and
+// kv = qkv[:, C:] (both at pitch 3C) they store what those store, bit for bit.  Forward and dQ run
+// on ceil(T / 64) query blocks and loop over the key blocks below key_len; dK/dV runs on
+// ceil(S / 64) key blocks and loops over the query blocks.  TAIL = T or S is not a multiple of
+// 64: every clamp, zero fill, lse / Dv guard and store guard uses the length of the tensor its
+// rows come from.  The dropout element index is (b*H + h)*T*S + q*S + key.
+struct CrossArgs {
+  const bf16_t* q;     // [B*T] rows of H*D, pitch ldq
+  const bf16_t* kv;    // [B*S] rows of 2*H*D, pitch ldkv
+  const bf16_t* dout;  // dctx [B*T][H*D] (bwd)
+  bf16_t* ctx;         // fwd output [B*T][H*D]
+  bf16_t* dq;          // bwd output [B*T][H*D]
+  bf16_t* dkv;         // bwd output [B*S][2*H*D]
+  float* lse;          // [B][H][T] (log2 domain)
+  float* dvec;         // [B][H][T] rowsum(dO*O)
+  const int* key_len;  // [B] or null
+  long ldq, ldkv;
+  int B, T, S, H;
+  float scale;
+  DropCfg drop;
+};
+
+template <bool TAIL>
+__global__ void __launch_bounds__(256) attn_cross_fwd_kernel(CrossArgs a) {
+  __shared__ __attribute__((aligned(16))) short Ks[KB * LDT];
+  __shared__ __attribute__((aligned(16))) short Vs[KB * LDT];
+  __shared__ __attribute__((aligned(16))) short Ps[4][16 * PLD];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = blockIdx.z, h = blockIdx.y, bx = blockIdx.x;
+  const int T = a.T, S = a.S, H = a.H, C = H * D;
+  const long ldkv = a.ldkv;
+  const int q0 = bx * QB + wave * 16;
+  int klen = a.key_len ? a.key_len[b] : S;
+  klen = klen < 1 ? 1 : (klen > S ? S : klen);
+  const bf16_t* kbase = a.kv + (long)b * S * ldkv + h * D;
+  const bf16_t* qrow = a.q + ((long)b * T + frag_row<TAIL>(q0 + (lane & 15), T)) * a.ldq + h * D;
+  const bf16x8 qf0 = gfrag(qrow, 0, lane), qf1 = gfrag(qrow, 1, lane);
+  const float c2 = a.scale * LOG2E;
+  const long bh = (long)b * H + h;
+  const uint64_t bhts = (uint64_t)bh * T * S;  // dropout index of element (q, key): bhts + q*S + key
+
+  f4v o[4];
+  float m[4], l[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) o[t] = f4v{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    m[r] = -INFINITY;
+    l[r] = 0.f;
+  }
+  short* slab = Ps[wave];
+  const int nkb = (klen + KB - 1) / KB;  // key blocks entirely past key_len are not read
+  for (int kb = 0; kb < nkb; ++kb) {
+    const int k0 = kb * KB;
+    __syncthreads();
+    tile_load<TAIL>(Ks, kbase + (long)k0 * ldkv, ldkv, tid, S - k0);
+    tile_load<TAIL>(Vs, kbase + (long)k0 * ldkv + C, ldkv, tid, S - k0);
+    __syncthreads();
+    f4v s[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      s[t] = f4v{0.f, 0.f, 0.f, 0.f};
+      s[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf0, read_frag<64, true>(Ks, t * 16, 0, lane), s[t], 0, 0, 0);
+      s[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf1, read_frag<64, true>(Ks, t * 16, 32, lane), s[t], 0, 0, 0);
+    }
+    float alpha[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      float mx = -INFINITY;
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const int key = k0 + t * 16 + (lane & 15);
+        const float v = key < klen ? s[t][r] * c2 : -INFINITY;
+        s[t][r] = v;
+        mx = fmaxf(mx, v);
+      }
+      mx = grp16_max(mx);
+      const float mn = fmaxf(m[r], mx);
+      alpha[r] = exp2f(m[r] - mn);
+      m[r] = mn;
+      float ls = 0.f;
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const float p = exp2f(s[t][r] - mn);
+        ls += p;
+        s[t][r] = p;
+      }
+      l[r] = l[r] * alpha[r] + ls;
+    }
+    if (a.drop.on) {
+#pragma unroll
+      for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const uint32_t q = q0 + (lane >> 4) * 4 + r;
+          const uint32_t key = k0 + t * 16 + (lane & 15);
+          s[t][r] *= drop_mul(a.drop, bhts + (q * (uint32_t)S + key));
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) o[t][r] *= alpha[r];
+    slab_store(slab, s, lane);
+    __builtin_amdgcn_wave_barrier();
+    const bf16x8 p0 = slab_frag(slab, 0, lane), p1 = slab_frag(slab, 1, lane);
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      o[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(p0, read_frag<64, false>(Vs, t * 16, 0, lane), o[t], 0, 0, 0);
+      o[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(p1, read_frag<64, false>(Vs, t * 16, 32, lane), o[t], 0, 0, 0);
+    }
+    __builtin_amdgcn_wave_barrier();
+  }
+  float inv[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const float lt = grp16_sum(l[r]);
+    inv[r] = 1.f / lt;
+    if ((lane & 15) == 0 && (!TAIL || q0 + (lane >> 4) * 4 + r < T))
+      a.lse[bh * T + q0 + (lane >> 4) * 4 + r] = m[r] + log2f(lt);
+  }
+  // normalise, stage through the wave slab, 16-B row stores
+#pragma unroll
+  for (int t = 0; t < 4; ++t)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) o[t][r] *= inv[r];
+  slab_store(slab, o, lane);
+  __builtin_amdgcn_wave_barrier();
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int c = lane + i * 64;  // 16 rows x 8 chunks
+    const int r = c >> 3, col = (c & 7) * 8;
+    if (!TAIL || q0 + r < T)
+      *reinterpret_cast<s8v*>(a.ctx + ((long)b * T + q0 + r) * C + h * D + col) =
+          *reinterpret_cast<const s8v*>(slab + r * PLD + col);
+  }
+}
+
+// grid: ceil(S / 64) key blocks; rows of keys >= key_len[b] are stored as exact zeros
+template <bool TAIL>
+__global__ void __launch_bounds__(256) attn_cross_bwd_dkv_kernel(CrossArgs a) {
+  __shared__ __attribute__((aligned(16))) short Qs[QB * LDT];
+  __shared__ __attribute__((aligned(16))) short Gs[QB * LDT];  // dO
+  __shared__ __attribute__((aligned(16))) short Ps[4][16 * PLD];
+  __shared__ __attribute__((aligned(16))) short Ds[4][16 * PLD];
+  __shared__ float lse_s[QB], dv_s[QB];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = blockIdx.z, h = blockIdx.y, bx = blockIdx.x;
+  const int T = a.T, S = a.S, H = a.H, C = H * D;
+  const long ldq = a.ldq, ldkv = a.ldkv;
+  const int k0 = bx * KB + wave * 16;  // this wave's 16 keys
+  int klen = a.key_len ? a.key_len[b] : S;
+  klen = klen < 1 ? 1 : (klen > S ? S : klen);
+  const long bh = (long)b * H + h;
+  const uint64_t bhts = (uint64_t)bh * T * S;  // dropout index of element (q, key): bhts + q*S + key
+  const bf16_t* qbase = a.q + (long)b * T * ldq + h * D;
+  const bf16_t* gbase = a.dout + (long)b * T * C + h * D;
+  const bf16_t* krow = a.kv + ((long)b * S + frag_row<TAIL>(k0 + (lane & 15), S)) * ldkv + h * D;
+  const bf16_t* vrow = krow + C;
+  const bf16x8 kf0 = gfrag(krow, 0, lane), kf1 = gfrag(krow, 1, lane);
+  const bf16x8 vf0 = gfrag(vrow, 0, lane), vf1 = gfrag(vrow, 1, lane);
+  const float c2 = a.scale * LOG2E;
+  f4v dk[4], dv[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) dk[t] = dv[t] = f4v{0.f, 0.f, 0.f, 0.f};
+  short* pslab = Ps[wave];
+  short* dslab = Ds[wave];
+  const bool any_valid = (uint32_t)bx * KB < (uint32_t)klen;
+  const int nqb = any_valid ? (T + QB - 1) / QB : 0;
+  for (int qb = 0; qb < nqb; ++qb) {
+    const int q0 = qb * QB;
+    __syncthreads();
+    tile_load<TAIL>(Qs, qbase + (long)q0 * ldq, ldq, tid, T - q0);
+    tile_load<TAIL>(Gs, gbase + (long)q0 * C, C, tid, T - q0);
+    if (tid < QB) {
+      const bool live = !TAIL || q0 + tid < T;  // queries >= T: no lse / Dv entry exists
+      lse_s[tid] = live ? a.lse[bh * T + q0 + tid] : 0.f;
+      dv_s[tid] = live ? a.dvec[bh * T + q0 + tid] : 0.f;
+    }
+    __syncthreads();
+    // S^T: rows = keys (this wave), cols = queries
+    f4v p[4], dp[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      p[t] = f4v{0.f, 0.f, 0.f, 0.f};
+      p[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf0, read_frag<64, true>(Qs, t * 16, 0, lane), p[t], 0, 0, 0);
+      p[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf1, read_frag<64, true>(Qs, t * 16, 32, lane), p[t], 0, 0, 0);
+      dp[t] = f4v{0.f, 0.f, 0.f, 0.f};
+      dp[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf0, read_frag<64, true>(Gs, t * 16, 0, lane), dp[t], 0, 0, 0);
+      dp[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf1, read_frag<64, true>(Gs, t * 16, 32, lane), dp[t], 0, 0, 0);
+    }
+    f4v pd[4], ds[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const int qi = t * 16 + (lane & 15);
+      const float ls = lse_s[qi], dvq = dv_s[qi];
+      const bool qlive = !TAIL || q0 + qi < T;  // a query column >= T adds p = dS = 0
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int key = k0 + (lane >> 4) * 4 + r;
+        const float pr = (key < klen && qlive) ? exp2f(p[t][r] * c2 - ls) : 0.f;
+        const float mul =
+            a.drop.on ? drop_mul(a.drop, bhts + ((uint32_t)(q0 + qi) * (uint32_t)S + (uint32_t)key)) : 1.f;
+        pd[t][r] = pr * mul;
+        ds[t][r] = pr * (dp[t][r] * mul - dvq);
+      }
+    }
+    slab_store(pslab, pd, lane);
+    slab_store(dslab, ds, lane);
+    __builtin_amdgcn_wave_barrier();
+    const bf16x8 pa0 = slab_frag(pslab, 0, lane), pa1 = slab_frag(pslab, 1, lane);
+    const bf16x8 da0 = slab_frag(dslab, 0, lane), da1 = slab_frag(dslab, 1, lane);
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      dv[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pa0, read_frag<64, false>(Gs, t * 16, 0, lane), dv[t], 0, 0, 0);
+      dv[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pa1, read_frag<64, false>(Gs, t * 16, 32, lane), dv[t], 0, 0, 0);
+      dk[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(da0, read_frag<64, false>(Qs, t * 16, 0, lane), dk[t], 0, 0, 0);
+      dk[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(da1, read_frag<64, false>(Qs, t * 16, 32, lane), dk[t], 0, 0, 0);
+    }
+    __builtin_amdgcn_wave_barrier();
+  }
+#pragma unroll
+  for (int t = 0; t < 4; ++t)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) dk[t][r] *= a.scale;
+  // stage through the slabs -> 16-B stores into dkv (K and V halves)
+  slab_store(pslab, dk, lane);
+  slab_store(dslab, dv, lane);
+  __builtin_amdgcn_wave_barrier();
+  bf16_t* drow = a.dkv + ((long)b * S + k0) * (2L * C) + h * D;
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int c = lane + i * 64;
+    const int r = c >> 3, col = (c & 7) * 8;
+    if (!TAIL || k0 + r < S) {
+      *reinterpret_cast<s8v*>(drow + (long)r * (2L * C) + col) = *reinterpret_cast<const s8v*>(pslab + r * PLD + col);
+      *reinterpret_cast<s8v*>(drow + (long)r * (2L * C) + C + col) =
+          *reinterpret_cast<const s8v*>(dslab + r * PLD + col);
+    }
+  }
+}
+
+// grid: ceil(T / 64) query blocks; three waves per SIMD asked for, like the tail variants above
+template <bool TAIL>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) attn_cross_bwd_dq_kernel(CrossArgs a) {
+  __shared__ __attribute__((aligned(16))) short Ks[KB * LDT];
+  __shared__ __attribute__((aligned(16))) short Vs[KB * LDT];
+  __shared__ __attribute__((aligned(16))) short Ds[4][16 * PLD];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = blockIdx.z, h = blockIdx.y, bx = blockIdx.x;
+  const int T = a.T, S = a.S, H = a.H, C = H * D;
+  const long ldkv = a.ldkv;
+  const int q0 = bx * QB + wave * 16;
+  int klen = a.key_len ? a.key_len[b] : S;
+  klen = klen < 1 ? 1 : (klen > S ? S : klen);
+  const long bh = (long)b * H + h;
+  const uint64_t bhts = (uint64_t)bh * T * S;  // dropout index of element (q, key): bhts + q*S + key
+  const bf16_t* kbase = a.kv + (long)b * S * ldkv + h * D;
+  const long qr = (long)b * T + frag_row<TAIL>(q0 + (lane & 15), T);
+  const bf16_t* qrow = a.q + qr * a.ldq + h * D;
+  const bf16_t* grow = a.dout + qr * C + h * D;
+  const bf16x8 qf0 = gfrag(qrow, 0, lane), qf1 = gfrag(qrow, 1, lane);
+  const bf16x8 gf0 = gfrag(grow, 0, lane), gf1 = gfrag(grow, 1, lane);
+  const float c2 = a.scale * LOG2E;
+  float ls[4], dvq[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int q = frag_row<TAIL>(q0 + (lane >> 4) * 4 + r, T);
+    ls[r] = a.lse[bh * T + q];
+    dvq[r] = a.dvec[bh * T + q];
+  }
+  f4v dq[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) dq[t] = f4v{0.f, 0.f, 0.f, 0.f};
+  short* dslab = Ds[wave];
+  const int nkb = (klen + KB - 1) / KB;  // key blocks entirely past key_len are not read
+  for (int kb = 0; kb < nkb; ++kb) {
+    const int k0 = kb * KB;
+    __syncthreads();
+    tile_load<TAIL>(Ks, kbase + (long)k0 * ldkv, ldkv, tid, S - k0);
+    tile_load<TAIL>(Vs, kbase + (long)k0 * ldkv + C, ldkv, tid, S - k0);
+    __syncthreads();
+    f4v s[4], dp[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      s[t] = f4v{0.f, 0.f, 0.f, 0.f};
+      s[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf0, read_frag<64, true>(Ks, t * 16, 0, lane), s[t], 0, 0, 0);
+      s[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf1, read_frag<64, true>(Ks, t * 16, 32, lane), s[t], 0, 0, 0);
+      dp[t] = f4v{0.f, 0.f, 0.f, 0.f};
+      dp[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(gf0, read_frag<64, true>(Vs, t * 16, 0, lane), dp[t], 0, 0, 0);
+      dp[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(gf1, read_frag<64, true>(Vs, t * 16, 32, lane), dp[t], 0, 0, 0);
+    }
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const int key = k0 + t * 16 + (lane & 15);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const uint32_t q = q0 + (lane >> 4) * 4 + r;
+        const float pr = key < klen ? exp2f(s[t][r] * c2 - ls[r]) : 0.f;
+        const float mul = a.drop.on ? drop_mul(a.drop, bhts + (q * (uint32_t)S + (uint32_t)key)) : 1.f;
+        s[t][r] = pr * (dp[t][r] * mul - dvq[r]);
+      }
+    }
+    slab_store(dslab, s, lane);
+    __builtin_amdgcn_wave_barrier();
+    const bf16x8 d0 = slab_frag(dslab, 0, lane), d1 = slab_frag(dslab, 1, lane);
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      dq[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(d0, read_frag<64, false>(Ks, t * 16, 0, lane), dq[t], 0, 0, 0);
+      dq[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(d1, read_frag<64, false>(Ks, t * 16, 32, lane), dq[t], 0, 0, 0);
+    }
+    __builtin_amdgcn_wave_barrier();
+  }
+#pragma unroll
+  for (int t = 0; t < 4; ++t)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) dq[t][r] *= a.scale;
+  slab_store(dslab, dq, lane);
+  __builtin_amdgcn_wave_barrier();
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int c = lane + i * 64;
+    const int r = c >> 3, col = (c & 7) * 8;
+    if (!TAIL || q0 + r < T)
+      *reinterpret_cast<s8v*>(a.dq + ((long)b * T + q0 + r) * C + h * D + col) =
+          *reinterpret_cast<const s8v*>(dslab + r * PLD + col);
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Fused backward for short sequences (S = 64 or 128, BERT fine-tuning): ONE workgroup per
 // (batch, head) holds the whole head in LDS, so the three-kernel path's prep pass, its
 // second recomputation of P / dP / the dropout hash (dQ kernel) and its per-block reloads
@@ -859,6 +1195,13 @@ void launch_bwd_fused(const AttnArgs& a, hipStream_t s) {
   else attn_bwd_fused_kernel<64, CAUSAL><<<a.B * a.H, 256, 0, s>>>(a);
 }
 
+bool cross_shape_ok(int B, int T, int S, int H) {
+  return B > 0 && T > 0 && S > 0 && H > 0 && (long)T * S <= 0x7fffffffL;  // q*S + key is a 32-bit index
+}
+bool cross_tail(const CrossArgs& a) { return a.T % QB != 0 || a.S % KB != 0; }
+dim3 cross_qgrid(const CrossArgs& a) { return dim3((a.T + QB - 1) / QB, a.H, a.B); }
+dim3 cross_kgrid(const CrossArgs& a) { return dim3((a.S + KB - 1) / KB, a.H, a.B); }
+
 // CLOUD_AMD_ATTN_FUSED_BWD=0 keeps the three-kernel backward at S <= 128 (A/B runs)
 bool fused_bwd_enabled() {
   static int v = -1;
@@ -915,6 +1258,43 @@ int ca_attn_bwd(const bf16_t* qkv, const bf16_t* out, const bf16_t* dout, const 
   CA_LAUNCH_CHECK();
   if (causal) launch_bwd_dq<true>(a, s);
   else launch_bwd_dq<false>(a, s);
+  CA_LAUNCH_CHECK();
+  return 0;
+}
+
+// Cross-attention: ctx[B*T][H*64] = softmax(Q K^T * scale + keymask) (dropout) V for q rows at pitch
+// ldq and kv = K | V rows at pitch ldkv (elements; multiples of 8, 16-byte aligned bases);
+// lse[B][H][T] saved for the backward.
+int ca_attn_cross_fwd(const bf16_t* q, const bf16_t* kv, bf16_t* ctx, float* lse, const int* key_len, int B, int T,
+                      int S, int H, long ldq, long ldkv, float scale, float p_drop, uint64_t seed, hipStream_t s) {
+  if (!cross_shape_ok(B, T, S, H)) return -1;
+  CrossArgs a{};
+  a.q = q; a.kv = kv; a.ctx = ctx; a.lse = lse; a.key_len = key_len; a.ldq = ldq; a.ldkv = ldkv;
+  a.B = B; a.T = T; a.S = S; a.H = H; a.scale = scale; a.drop = make_drop(p_drop, seed);
+  if (cross_tail(a)) attn_cross_fwd_kernel<true><<<cross_qgrid(a), 256, 0, s>>>(a);
+  else attn_cross_fwd_kernel<false><<<cross_qgrid(a), 256, 0, s>>>(a);
+  CA_LAUNCH_CHECK();
+  return 0;
+}
+
+// dq[B*T][H*64] and dkv[B*S][2*H*64] (every row written) from dctx; dvec: [B][H][T] fp32 scratch.
+int ca_attn_cross_bwd(const bf16_t* q, const bf16_t* kv, const bf16_t* out, const bf16_t* dout, const float* lse,
+                      float* dvec, bf16_t* dq, bf16_t* dkv, const int* key_len, int B, int T, int S, int H, long ldq,
+                      long ldkv, float scale, float p_drop, uint64_t seed, hipStream_t s) {
+  if (!cross_shape_ok(B, T, S, H)) return -1;
+  AttnArgs p{};  // Dv = rowsum(dO * O) over the B*T query rows
+  p.out = out; p.dout = dout; p.dvec = dvec; p.B = B; p.S = T; p.H = H;
+  attn_bwd_prep_kernel<<<ca_cdiv((long)B * T * H, 32), 256, 0, s>>>(p);
+  CA_LAUNCH_CHECK();
+  CrossArgs a{};
+  a.q = q; a.kv = kv; a.dout = dout; a.lse = const_cast<float*>(lse); a.dvec = dvec; a.dq = dq; a.dkv = dkv;
+  a.key_len = key_len; a.ldq = ldq; a.ldkv = ldkv;
+  a.B = B; a.T = T; a.S = S; a.H = H; a.scale = scale; a.drop = make_drop(p_drop, seed);
+  if (cross_tail(a)) attn_cross_bwd_dkv_kernel<true><<<cross_kgrid(a), 256, 0, s>>>(a);
+  else attn_cross_bwd_dkv_kernel<false><<<cross_kgrid(a), 256, 0, s>>>(a);
+  CA_LAUNCH_CHECK();
+  if (cross_tail(a)) attn_cross_bwd_dq_kernel<true><<<cross_qgrid(a), 256, 0, s>>>(a);
+  else attn_cross_bwd_dq_kernel<false><<<cross_qgrid(a), 256, 0, s>>>(a);
   CA_LAUNCH_CHECK();
   return 0;
 }
