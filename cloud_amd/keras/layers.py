@@ -382,8 +382,18 @@ class MultiHeadAttention(Layer):
     not ``value``) without a mask, returned scores or the causal flag is native under the same
     conditions: the Q projection from the first third of ``qkv_kernel``, the K | V projection
     from the other two as one GEMM (two and a concatenation when ``key`` is a tensor of its own),
-    ``ops.cross_attention`` and the output projection.  Everything else (an explicit mask,
-    returned scores, causal cross-attention) is the same math in PyTorch.
+    ``ops.cross_attention`` and the output projection.  An ``attention_mask`` (any shape Keras
+    broadcasts to ``[B, T, S]``, or per head ``[B, H, T, S]``; torch or numpy; with or without the
+    causal flag) and causal cross-attention (the top-left ``tril`` of ``[T, S]``) are native under
+    the same conditions too, same projections, with the mask handed to ``ops.attention(mask=)`` /
+    ``ops.cross_attention(mask=)``.  Everything else (float32 layers, CPU, another ``key_dim``,
+    returned scores) is the same math in PyTorch.
+
+    One difference between the two: a query row whose mask allows no key at all gets a zero
+    context on the native route (the kernels define a softmax over nothing as zeros, and such a
+    row sends no gradient), where the PyTorch branch, like Keras, fills with ``finfo.min`` and so
+    returns the mean of the values.  Padded query rows are the usual case and are discarded
+    downstream either way.
 
     Calls: Keras style ``layer(query, value, key=None, attention_mask=None,
     use_causal_mask=False, return_attention_scores=False, training=None)``, or the list form
@@ -466,7 +476,7 @@ class MultiHeadAttention(Layer):
             qkv = dense_op(query.to(dt), self.qkv_kernel, self.qkv_bias, None)
             ctx = ops.attention(qkv, H, None, p, bool(training), causal=causal)
             return dense_op(ctx, self.out_kernel, self.out_bias, None)
-        if attention_mask is None and not return_attention_scores and not causal:
+        def cross_proj():  # Q from the first third of the packed kernel, K | V from the other two
             bias = self.qkv_bias
             q = dense_op(query.to(dt), self.qkv_kernel[:hd], None if bias is None else bias[:hd], None)
             if key is value:  # K | V are adjacent row blocks of the packed kernel: one GEMM
@@ -475,7 +485,31 @@ class MultiHeadAttention(Layer):
                 k = dense_op(key.to(dt), self.qkv_kernel[hd:2 * hd], None if bias is None else bias[hd:2 * hd], None)
                 v = dense_op(value.to(dt), self.qkv_kernel[2 * hd:], None if bias is None else bias[2 * hd:], None)
                 kv = torch.cat([k, v], dim=-1)
+            return q, kv
+
+        if attention_mask is None and not return_attention_scores and not causal:
+            q, kv = cross_proj()
             ctx = ops.cross_attention(q, kv, H, None, p, bool(training))
+            return dense_op(ctx, self.out_kernel, self.out_bias, None)
+        if (not return_attention_scores and dt == torch.bfloat16 and D == 64
+                and ops.use_native(query, value, key)):
+            # masked attention (an attention_mask, or causal cross-attention) on the mask kernels
+            allowed = None
+            if attention_mask is not None:
+                allowed = torch.as_tensor(attention_mask, device=query.device).bool()
+                while allowed.dim() < 3:
+                    allowed = allowed[None]
+                if allowed.dim() == 3:
+                    allowed = allowed[:, None]  # heads
+            if query is value and key is value:
+                qkv = dense_op(query.to(dt), self.qkv_kernel, self.qkv_bias, None)
+                ctx = ops.attention(qkv, H, None, p, bool(training), causal=causal, mask=allowed)
+            else:
+                if causal:
+                    tri = torch.ones(query.shape[1], key.shape[1], dtype=torch.bool, device=query.device).tril()
+                    allowed = tri if allowed is None else allowed & tri
+                q, kv = cross_proj()
+                ctx = ops.cross_attention(q, kv, H, None, p, bool(training), mask=allowed)
             return dense_op(ctx, self.out_kernel, self.out_bias, None)
 
         def proj(x, i):

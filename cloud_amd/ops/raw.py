@@ -911,8 +911,10 @@ def attn_bwd(qkv, ctx, dctx, lse, B, S, H, key_len=None, p_drop=0.0, seed=0, sca
     return dqkv
 
 
-def _cross_operands(q, kv, B, T, S, H):
-    """The shape, pitch and alignment contract of the cross-attention kernels (16-byte loads)."""
+def _cross_operands(q, kv, B, T, S, H, mask=None):
+    """The shape, pitch and alignment contract of the cross-attention kernels (16-byte loads), and
+    of their byte mask.  Returns the mask's ``(pointer, batch, head, row)`` element strides with 0
+    for its size-1 (broadcast) axes; ``(0, 0, 0, 0)`` without a mask."""
     C = H * 64
     for name, t, shape in (("q", q, (B * T, C)), ("kv", kv, (B * S, 2 * C))):
         if t.dtype != torch.bfloat16 or tuple(t.shape) != shape:
@@ -924,28 +926,51 @@ def _cross_operands(q, kv, B, T, S, H):
             raise ValueError(f"attn_cross: {name} must start on a 16-byte boundary")
     if B < 1 or T < 1 or S < 1 or H < 1 or T * S >= 2 ** 31:
         raise ValueError(f"attn_cross: B, T, S, H must be >= 1 and T * S < 2^31, got {(B, T, S, H)}")
+    if mask is None:
+        return 0, 0, 0, 0
+    if mask.dtype not in (torch.bool, torch.uint8):
+        raise ValueError(f"attn_cross: mask must be torch.bool or torch.uint8, got {mask.dtype}")
+    if mask.dim() != 4 or mask.shape[3] != S or any(n not in (1, full) for n, full in zip(mask.shape, (B, H, T))):
+        raise ValueError(f"attn_cross: mask must be [B|1, H|1, T|1, S] = [{B}|1, {H}|1, {T}|1, {S}], "
+                         f"got {tuple(mask.shape)}")
+    if mask.device != q.device:
+        raise ValueError(f"attn_cross: mask is on {mask.device}, q on {q.device}")
+    if S > 1 and mask.stride(3) != 1:
+        raise ValueError(f"attn_cross: mask needs unit key stride, got strides {tuple(mask.stride())}")
+    sb, sh, st = (0 if mask.shape[i] == 1 else mask.stride(i) for i in range(3))
+    if min(sb, sh, st) < 0 or (T - 1) * st + S >= 2 ** 31:
+        raise ValueError("attn_cross: mask strides must be >= 0 and a (batch, head) slice must span less than "
+                         f"2^31 bytes, got strides {tuple(mask.stride())}")
+    return mask.data_ptr(), sb, sh, st
 
 
-def attn_cross_fwd(q, kv, B, T, S, H, key_len=None, p_drop=0.0, seed=0, scale=None):
+def attn_cross_fwd(q, kv, B, T, S, H, key_len=None, p_drop=0.0, seed=0, scale=None, *, mask=None):
     """Cross-attention: q [B*T, H*64] and kv [B*S, 2*H*64] (K | V) -> (ctx [B*T, H*64], lse [B, H, T]).
     Any T and S; both operands may be column slices of wider tensors (unit column stride, the
     row pitch is ``stride(0)``).  ``key_len`` [B] int32: the number of valid leading keys, clamped
-    to [1, S].  The dropout element index is ``(b*H + h)*T*S + q*S + key``."""
+    to [1, S].  The dropout element index is ``(b*H + h)*T*S + q*S + key``.
+
+    ``mask``: ``torch.bool`` / ``torch.uint8`` ``[B|1, H|1, T|1, S]`` on the same device, unit key
+    stride, any other strides (size-1 axes are broadcast, nothing is materialised).  Query ``q``
+    sees ``key`` iff ``key < key_len[b]`` and its mask byte is non-zero.  A query that sees no key
+    gets a zero context row and ``lse = 0``."""
     ext = _ext.load(required=True)
-    _cross_operands(q, kv, B, T, S, H)
+    mptr, msb, msh, mst = _cross_operands(q, kv, B, T, S, H, mask)
     ctx = torch.empty((B * T, H * 64), dtype=torch.bfloat16, device=q.device)
     lse = torch.empty((B, H, T), dtype=torch.float32, device=q.device)
     scale = 1.0 / 8.0 if scale is None else scale
-    ext.attn_cross_fwd(q.data_ptr(), kv.data_ptr(), ctx.data_ptr(), lse.data_ptr(), _ext.ptr(key_len), B, T, S, H,
-                       q.stride(0), kv.stride(0), float(scale), float(p_drop), int(seed), _st(q.device))
+    ext.attn_cross_fwd(q.data_ptr(), kv.data_ptr(), ctx.data_ptr(), lse.data_ptr(), _ext.ptr(key_len), mptr, msb, msh,
+                       mst, B, T, S, H, q.stride(0), kv.stride(0), float(scale), float(p_drop), int(seed),
+                       _st(q.device))
     return ctx, lse
 
 
-def attn_cross_bwd(q, kv, ctx, dctx, lse, B, T, S, H, key_len=None, p_drop=0.0, seed=0, scale=None):
+def attn_cross_bwd(q, kv, ctx, dctx, lse, B, T, S, H, key_len=None, p_drop=0.0, seed=0, scale=None, *, mask=None):
     """-> (dq [B*T, H*64], dkv [B*S, 2*H*64]), both contiguous; ``ctx`` and ``dctx`` are contiguous
-    [B*T, H*64].  dK / dV rows of keys >= key_len are zeros."""
+    [B*T, H*64].  dK / dV rows of keys >= key_len are zeros.  ``mask`` as in ``attn_cross_fwd`` (the
+    same one): dQ rows of queries that see no key and dK / dV rows of keys no query sees are zeros."""
     ext = _ext.load(required=True)
-    _cross_operands(q, kv, B, T, S, H)
+    mptr, msb, msh, mst = _cross_operands(q, kv, B, T, S, H, mask)
     C = H * 64
     for name, t in (("ctx", ctx), ("dctx", dctx)):
         if t.dtype != torch.bfloat16 or tuple(t.shape) != (B * T, C) or not t.is_contiguous():
@@ -955,8 +980,8 @@ def attn_cross_bwd(q, kv, ctx, dctx, lse, B, T, S, H, key_len=None, p_drop=0.0, 
     dvec = torch.empty_like(lse)
     scale = 1.0 / 8.0 if scale is None else scale
     ext.attn_cross_bwd(q.data_ptr(), kv.data_ptr(), ctx.data_ptr(), dctx.data_ptr(), lse.data_ptr(), dvec.data_ptr(),
-                       dq.data_ptr(), dkv.data_ptr(), _ext.ptr(key_len), B, T, S, H, q.stride(0), kv.stride(0),
-                       float(scale), float(p_drop), int(seed), _st(q.device))
+                       dq.data_ptr(), dkv.data_ptr(), _ext.ptr(key_len), mptr, msb, msh, mst, B, T, S, H, q.stride(0),
+                       kv.stride(0), float(scale), float(p_drop), int(seed), _st(q.device))
     return dq, dkv
 
 

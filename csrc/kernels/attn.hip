@@ -37,7 +37,9 @@
 // dropout element index is the same in both modes.
 //
 // Cross-attention (queries and keys / values in separate tensors, own lengths and row pitches)
-// has three generic kernels of its own below the self-attention ones: see CrossArgs.
+// has three generic kernels of its own below the self-attention ones: see CrossArgs.  They also
+// take an arbitrary byte mask (MASK, a compile-time parameter like TAIL), which is how masked
+// self-attention runs: on the Q and K | V column views of the packed qkv.
 #include "ca_mfma_core.h"
 #include "ca_rng.h"
 
@@ -516,6 +518,14 @@ attn_bwd_dq_kernel(AttnArgs a) {
 // ceil(S / 64) key blocks and loops over the query blocks.  TAIL = T or S is not a multiple of
 // 64: every clamp, zero fill, lse / Dv guard and store guard uses the length of the tensor its
 // rows come from.  The dropout element index is (b*H + h)*T*S + q*S + key.
+//
+// MASK: a byte per score, read through strides (0 = broadcast axis, key stride 1): the score of
+// (b, h, q, key) takes part iff key < key_len[b] and mask[b*msb + h*msh + q*mst + key] != 0; key
+// blocks at or past key_len are still not read.  A query that sees no key is possible then: its
+// context is exactly 0, its lse is stored as 0, and it adds exactly 0 to dQ, dK and dV (the
+// backward selects p = 0 for a hidden element, it never multiplies by a masked exp2f); a key no
+// query sees gets exact-zero dK / dV rows.  Every statement of it is under if constexpr (MASK):
+// the MASK = false instantiations are the kernels as they were.
 struct CrossArgs {
   const bf16_t* q;     // [B*T] rows of H*D, pitch ldq
   const bf16_t* kv;    // [B*S] rows of 2*H*D, pitch ldkv
@@ -530,9 +540,98 @@ struct CrossArgs {
   int B, T, S, H;
   float scale;
   DropCfg drop;
+  const uint8_t* mask;  // MASK: element (b, h, q, key) at b*msb + h*msh + q*mst + key, != 0 = visible
+  long msb, msh, mst;   // element strides; 0 = broadcast axis; (T - 1)*mst + S < 2^31
 };
 
+// MASK: the visibility bytes of a lane's 16 elements of a 64x64 score block, packed to bit 4t + r
+// for the element of C tile t, register r.
+//
+// Forward and dQ (queries on rows): element (t, r) is row 4 (lane >> 4) + r, key 16 t + (lane & 15),
+// so each of the 16 byte loads reads 16 consecutive bytes of 4 mask rows per wave, every byte of
+// the tile once per workgroup, at any alignment of the rows (S is arbitrary).  Offsets inside a
+// (batch, head) slice are 32-bit.  TAIL clamps the key to S - 1 (such an element is hidden by
+// key < key_len already) and the offset to the slice's last byte (rows >= T compute copies that
+// are never stored, whatever they see), so no byte past row T or key S is read.
+// The loads are issued before the K / V tile loads of the block and packed after them.
+struct MaskRaw {
+  uint32_t v[16];
+};
 template <bool TAIL>
+__device__ __forceinline__ MaskRaw mask_load_q(const uint8_t* mb, uint32_t mst, int row0, int k0, int T, int S, int lane) {
+  MaskRaw m;
+  if constexpr (TAIL) {
+    const uint32_t last = (uint32_t)(T - 1) * mst + (uint32_t)(S - 1);  // the slice's last byte
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const int kc = k0 + t * 16 + (lane & 15);
+      const uint32_t kt = (uint32_t)row0 * mst + (uint32_t)(kc < S ? kc : S - 1);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const uint32_t o = kt + (uint32_t)r * mst;  // rows >= T (never stored) read the last byte
+        m.v[t * 4 + r] = mb[o < last ? o : last];
+      }
+    }
+  } else {
+    const uint32_t vb = (uint32_t)row0 * mst + (uint32_t)(lane & 15);  // the only per-lane, loop-invariant part
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const uint32_t o = vb + ((uint32_t)k0 + (uint32_t)r * mst);
+#pragma unroll
+      for (int t = 0; t < 4; ++t) m.v[t * 4 + r] = mb[o + t * 16];
+    }
+  }
+  return m;
+}
+__device__ __forceinline__ uint32_t mask_pack_q(const MaskRaw& m) {
+  uint32_t bits = 0;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) bits |= (m.v[i] != 0 ? 1u : 0u) << i;
+  // pin the packed word: without this the compiler tests the 16 bytes where the bits are used and
+  // keeps them in registers through the whole block (the dQ kernel then spills)
+  asm volatile("" : "+v"(bits));
+  return bits;
+}
+
+// dK/dV (keys on rows): element (t, r) is key 4 (lane >> 4) + r of the wave's 16, query
+// 16 t + (lane & 15).  Reading that directly would put the 16 lanes of a row group on 16 mask rows
+// per load.  Instead load i reads the same shape as above -- queries 4 i + (lane >> 4), key
+// (lane & 15) of the wave's 16: 16 consecutive bytes of 4 rows -- and the transpose is done on the
+// wave's ballots: the 16 ballots are the wave's whole 64 x 16 visibility tile, bit 16 g' + c' of
+// ballot i being query 4 i + g', key c'.  Lane (g, c) takes, for tile t, ballot 4 t + (c >> 2) and
+// the 4 bits from 16 (c & 3) + 4 g.  No LDS, no alignment condition; TAIL clamps query and key.
+template <bool TAIL>
+__device__ __forceinline__ MaskRaw mask_load_k(const uint8_t* mb, uint32_t mst, int q0, int kw, int T, int S, int lane) {
+  MaskRaw m;
+  int key = kw + (lane & 15);
+  if constexpr (TAIL) key = key < S ? key : S - 1;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    if constexpr (TAIL) {
+      const int q = q0 + 4 * i + (lane >> 4);
+      m.v[i] = mb[(uint32_t)(q < T ? q : T - 1) * mst + (uint32_t)key];
+    } else {
+      const uint32_t vb = (uint32_t)(lane >> 4) * mst + (uint32_t)key;  // the only per-lane, loop-invariant part
+      m.v[i] = mb[vb + (uint32_t)(q0 + 4 * i) * mst];
+    }
+  }
+  return m;
+}
+__device__ __forceinline__ uint32_t mask_pack_k(const MaskRaw& m, int lane) {
+  const int sel = (lane & 15) >> 2, sh = 16 * (lane & 3) + 4 * (lane >> 4);
+  uint32_t bits = 0;
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const uint64_t b0 = __ballot(m.v[4 * t] != 0), b1 = __ballot(m.v[4 * t + 1] != 0);
+    const uint64_t b2 = __ballot(m.v[4 * t + 2] != 0), b3 = __ballot(m.v[4 * t + 3] != 0);
+    const uint64_t w = sel == 0 ? b0 : (sel == 1 ? b1 : (sel == 2 ? b2 : b3));
+    bits |= ((uint32_t)(w >> sh) & 0xFu) << (4 * t);
+  }
+  asm volatile("" : "+v"(bits));  // as in mask_pack_q
+  return bits;
+}
+
+template <bool TAIL, bool MASK>
 __global__ void __launch_bounds__(256) attn_cross_fwd_kernel(CrossArgs a) {
   __shared__ __attribute__((aligned(16))) short Ks[KB * LDT];
   __shared__ __attribute__((aligned(16))) short Vs[KB * LDT];
@@ -550,6 +649,8 @@ __global__ void __launch_bounds__(256) attn_cross_fwd_kernel(CrossArgs a) {
   const float c2 = a.scale * LOG2E;
   const long bh = (long)b * H + h;
   const uint64_t bhts = (uint64_t)bh * T * S;  // dropout index of element (q, key): bhts + q*S + key
+  const uint8_t* mb = nullptr;
+  if constexpr (MASK) mb = a.mask + b * a.msb + h * a.msh;
 
   f4v o[4];
   float m[4], l[4];
@@ -564,9 +665,13 @@ __global__ void __launch_bounds__(256) attn_cross_fwd_kernel(CrossArgs a) {
   const int nkb = (klen + KB - 1) / KB;  // key blocks entirely past key_len are not read
   for (int kb = 0; kb < nkb; ++kb) {
     const int k0 = kb * KB;
+    MaskRaw mraw;
+    if constexpr (MASK) mraw = mask_load_q<TAIL>(mb, (uint32_t)a.mst, q0 + (lane >> 4) * 4, k0, T, S, lane);
     __syncthreads();
     tile_load<TAIL>(Ks, kbase + (long)k0 * ldkv, ldkv, tid, S - k0);
     tile_load<TAIL>(Vs, kbase + (long)k0 * ldkv + C, ldkv, tid, S - k0);
+    uint32_t vis = 0;
+    if constexpr (MASK) vis = mask_pack_q(mraw);  // here: the mask bytes arrive before the tile's
     __syncthreads();
     f4v s[4];
 #pragma unroll
@@ -582,18 +687,24 @@ __global__ void __launch_bounds__(256) attn_cross_fwd_kernel(CrossArgs a) {
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
         const int key = k0 + t * 16 + (lane & 15);
-        const float v = key < klen ? s[t][r] * c2 : -INFINITY;
+        bool seen = key < klen;
+        if constexpr (MASK) seen = seen && ((vis >> (4 * t + r)) & 1u);
+        const float v = seen ? s[t][r] * c2 : -INFINITY;
         s[t][r] = v;
         mx = fmaxf(mx, v);
       }
       mx = grp16_max(mx);
       const float mn = fmaxf(m[r], mx);
-      alpha[r] = exp2f(m[r] - mn);
+      // MASK: a row that has seen no key yet has m = mn = -inf; subtracting 0 instead keeps
+      // alpha = p = exp2(-inf) = 0 where -inf - -inf would be NaN
+      float ms = mn;
+      if constexpr (MASK) ms = mn == -INFINITY ? 0.f : mn;
+      alpha[r] = exp2f(m[r] - ms);
       m[r] = mn;
       float ls = 0.f;
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
-        const float p = exp2f(s[t][r] - mn);
+        const float p = exp2f(s[t][r] - ms);
         ls += p;
         s[t][r] = p;
       }
@@ -628,8 +739,12 @@ __global__ void __launch_bounds__(256) attn_cross_fwd_kernel(CrossArgs a) {
   for (int r = 0; r < 4; ++r) {
     const float lt = grp16_sum(l[r]);
     inv[r] = 1.f / lt;
-    if ((lane & 15) == 0 && (!TAIL || q0 + (lane >> 4) * 4 + r < T))
-      a.lse[bh * T + q0 + (lane >> 4) * 4 + r] = m[r] + log2f(lt);
+    float lr = m[r] + log2f(lt);
+    if constexpr (MASK) {  // a row with no visible key: context 0, lse 0 (the backward selects p = 0)
+      inv[r] = lt > 0.f ? inv[r] : 0.f;
+      lr = lt > 0.f ? lr : 0.f;
+    }
+    if ((lane & 15) == 0 && (!TAIL || q0 + (lane >> 4) * 4 + r < T)) a.lse[bh * T + q0 + (lane >> 4) * 4 + r] = lr;
   }
   // normalise, stage through the wave slab, 16-B row stores
 #pragma unroll
@@ -649,7 +764,7 @@ __global__ void __launch_bounds__(256) attn_cross_fwd_kernel(CrossArgs a) {
 }
 
 // grid: ceil(S / 64) key blocks; rows of keys >= key_len[b] are stored as exact zeros
-template <bool TAIL>
+template <bool TAIL, bool MASK>
 __global__ void __launch_bounds__(256) attn_cross_bwd_dkv_kernel(CrossArgs a) {
   __shared__ __attribute__((aligned(16))) short Qs[QB * LDT];
   __shared__ __attribute__((aligned(16))) short Gs[QB * LDT];  // dO
@@ -679,8 +794,12 @@ __global__ void __launch_bounds__(256) attn_cross_bwd_dkv_kernel(CrossArgs a) {
   short* dslab = Ds[wave];
   const bool any_valid = (uint32_t)bx * KB < (uint32_t)klen;
   const int nqb = any_valid ? (T + QB - 1) / QB : 0;
+  const uint8_t* mb = nullptr;
+  if constexpr (MASK) mb = a.mask + b * a.msb + h * a.msh;
   for (int qb = 0; qb < nqb; ++qb) {
     const int q0 = qb * QB;
+    MaskRaw mraw;
+    if constexpr (MASK) mraw = mask_load_k<TAIL>(mb, (uint32_t)a.mst, q0, k0, T, S, lane);
     __syncthreads();
     tile_load<TAIL>(Qs, qbase + (long)q0 * ldq, ldq, tid, T - q0);
     tile_load<TAIL>(Gs, gbase + (long)q0 * C, C, tid, T - q0);
@@ -690,6 +809,8 @@ __global__ void __launch_bounds__(256) attn_cross_bwd_dkv_kernel(CrossArgs a) {
       dv_s[tid] = live ? a.dvec[bh * T + q0 + tid] : 0.f;
     }
     __syncthreads();
+    uint32_t vis = 0;
+    if constexpr (MASK) vis = mask_pack_k(mraw, lane);
     // S^T: rows = keys (this wave), cols = queries
     f4v p[4], dp[4];
 #pragma unroll
@@ -710,7 +831,9 @@ __global__ void __launch_bounds__(256) attn_cross_bwd_dkv_kernel(CrossArgs a) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int key = k0 + (lane >> 4) * 4 + r;
-        const float pr = (key < klen && qlive) ? exp2f(p[t][r] * c2 - ls) : 0.f;
+        bool seen = key < klen && qlive;
+        if constexpr (MASK) seen = seen && ((vis >> (4 * t + r)) & 1u);
+        const float pr = seen ? exp2f(p[t][r] * c2 - ls) : 0.f;
         const float mul =
             a.drop.on ? drop_mul(a.drop, bhts + ((uint32_t)(q0 + qi) * (uint32_t)S + (uint32_t)key)) : 1.f;
         pd[t][r] = pr * mul;
@@ -753,7 +876,7 @@ __global__ void __launch_bounds__(256) attn_cross_bwd_dkv_kernel(CrossArgs a) {
 }
 
 // grid: ceil(T / 64) query blocks; three waves per SIMD asked for, like the tail variants above
-template <bool TAIL>
+template <bool TAIL, bool MASK>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) attn_cross_bwd_dq_kernel(CrossArgs a) {
   __shared__ __attribute__((aligned(16))) short Ks[KB * LDT];
   __shared__ __attribute__((aligned(16))) short Vs[KB * LDT];
@@ -781,6 +904,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) a
     ls[r] = a.lse[bh * T + q];
     dvq[r] = a.dvec[bh * T + q];
   }
+  const uint8_t* mb = nullptr;
+  if constexpr (MASK) mb = a.mask + b * a.msb + h * a.msh;
   f4v dq[4];
 #pragma unroll
   for (int t = 0; t < 4; ++t) dq[t] = f4v{0.f, 0.f, 0.f, 0.f};
@@ -788,9 +913,13 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) a
   const int nkb = (klen + KB - 1) / KB;  // key blocks entirely past key_len are not read
   for (int kb = 0; kb < nkb; ++kb) {
     const int k0 = kb * KB;
+    MaskRaw mraw;
+    if constexpr (MASK) mraw = mask_load_q<TAIL>(mb, (uint32_t)a.mst, q0 + (lane >> 4) * 4, k0, T, S, lane);
     __syncthreads();
     tile_load<TAIL>(Ks, kbase + (long)k0 * ldkv, ldkv, tid, S - k0);
     tile_load<TAIL>(Vs, kbase + (long)k0 * ldkv + C, ldkv, tid, S - k0);
+    uint32_t vis = 0;
+    if constexpr (MASK) vis = mask_pack_q(mraw);  // here: the mask bytes arrive before the tile's
     __syncthreads();
     f4v s[4], dp[4];
 #pragma unroll
@@ -808,7 +937,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) a
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const uint32_t q = q0 + (lane >> 4) * 4 + r;
-        const float pr = key < klen ? exp2f(s[t][r] * c2 - ls[r]) : 0.f;
+        bool seen = key < klen;
+        if constexpr (MASK) seen = seen && ((vis >> (4 * t + r)) & 1u);
+        const float pr = seen ? exp2f(s[t][r] * c2 - ls[r]) : 0.f;
         const float mul = a.drop.on ? drop_mul(a.drop, bhts + (q * (uint32_t)S + (uint32_t)key)) : 1.f;
         s[t][r] = pr * (dp[t][r] * mul - dvq[r]);
       }
@@ -1201,6 +1332,28 @@ bool cross_shape_ok(int B, int T, int S, int H) {
 bool cross_tail(const CrossArgs& a) { return a.T % QB != 0 || a.S % KB != 0; }
 dim3 cross_qgrid(const CrossArgs& a) { return dim3((a.T + QB - 1) / QB, a.H, a.B); }
 dim3 cross_kgrid(const CrossArgs& a) { return dim3((a.S + KB - 1) / KB, a.H, a.B); }
+// mask strides: non-negative, and a (batch, head) slice addressable with 32-bit offsets
+bool cross_mask_ok(const uint8_t* mask, long sb, long sh, long st, int T, int S) {
+  return !mask || (sb >= 0 && sh >= 0 && st >= 0 && (long)(T - 1) * st + S <= 0x7fffffffL);
+}
+void cross_set_mask(CrossArgs& a, const uint8_t* mask, long sb, long sh, long st) {
+  a.mask = mask; a.msb = sb; a.msh = sh; a.mst = st;
+}
+template <bool MASK>
+void launch_cross_fwd(const CrossArgs& a, hipStream_t s) {
+  if (cross_tail(a)) attn_cross_fwd_kernel<true, MASK><<<cross_qgrid(a), 256, 0, s>>>(a);
+  else attn_cross_fwd_kernel<false, MASK><<<cross_qgrid(a), 256, 0, s>>>(a);
+}
+template <bool MASK>
+void launch_cross_bwd_dkv(const CrossArgs& a, hipStream_t s) {
+  if (cross_tail(a)) attn_cross_bwd_dkv_kernel<true, MASK><<<cross_kgrid(a), 256, 0, s>>>(a);
+  else attn_cross_bwd_dkv_kernel<false, MASK><<<cross_kgrid(a), 256, 0, s>>>(a);
+}
+template <bool MASK>
+void launch_cross_bwd_dq(const CrossArgs& a, hipStream_t s) {
+  if (cross_tail(a)) attn_cross_bwd_dq_kernel<true, MASK><<<cross_qgrid(a), 256, 0, s>>>(a);
+  else attn_cross_bwd_dq_kernel<false, MASK><<<cross_qgrid(a), 256, 0, s>>>(a);
+}
 
 // CLOUD_AMD_ATTN_FUSED_BWD=0 keeps the three-kernel backward at S <= 128 (A/B runs)
 bool fused_bwd_enabled() {
@@ -1265,23 +1418,29 @@ int ca_attn_bwd(const bf16_t* qkv, const bf16_t* out, const bf16_t* dout, const 
 // Cross-attention: ctx[B*T][H*64] = softmax(Q K^T * scale + keymask) (dropout) V for q rows at pitch
 // ldq and kv = K | V rows at pitch ldkv (elements; multiples of 8, 16-byte aligned bases);
 // lse[B][H][T] saved for the backward.
-int ca_attn_cross_fwd(const bf16_t* q, const bf16_t* kv, bf16_t* ctx, float* lse, const int* key_len, int B, int T,
-                      int S, int H, long ldq, long ldkv, float scale, float p_drop, uint64_t seed, hipStream_t s) {
-  if (!cross_shape_ok(B, T, S, H)) return -1;
+// mask (null = none): byte (b, h, q, key) at b*msb + h*msh + q*mst + key, element strides, 0 = broadcast;
+// a score takes part iff key < key_len[b] and its byte is non-zero.  A query that sees no key gets
+// context 0 and lse 0, and contributes 0 to every gradient.
+int ca_attn_cross_fwd(const bf16_t* q, const bf16_t* kv, bf16_t* ctx, float* lse, const int* key_len,
+                      const uint8_t* mask, long msb, long msh, long mst, int B, int T, int S, int H, long ldq,
+                      long ldkv, float scale, float p_drop, uint64_t seed, hipStream_t s) {
+  if (!cross_shape_ok(B, T, S, H) || !cross_mask_ok(mask, msb, msh, mst, T, S)) return -1;
   CrossArgs a{};
   a.q = q; a.kv = kv; a.ctx = ctx; a.lse = lse; a.key_len = key_len; a.ldq = ldq; a.ldkv = ldkv;
   a.B = B; a.T = T; a.S = S; a.H = H; a.scale = scale; a.drop = make_drop(p_drop, seed);
-  if (cross_tail(a)) attn_cross_fwd_kernel<true><<<cross_qgrid(a), 256, 0, s>>>(a);
-  else attn_cross_fwd_kernel<false><<<cross_qgrid(a), 256, 0, s>>>(a);
+  cross_set_mask(a, mask, msb, msh, mst);
+  if (mask) launch_cross_fwd<true>(a, s);
+  else launch_cross_fwd<false>(a, s);
   CA_LAUNCH_CHECK();
   return 0;
 }
 
 // dq[B*T][H*64] and dkv[B*S][2*H*64] (every row written) from dctx; dvec: [B][H][T] fp32 scratch.
 int ca_attn_cross_bwd(const bf16_t* q, const bf16_t* kv, const bf16_t* out, const bf16_t* dout, const float* lse,
-                      float* dvec, bf16_t* dq, bf16_t* dkv, const int* key_len, int B, int T, int S, int H, long ldq,
-                      long ldkv, float scale, float p_drop, uint64_t seed, hipStream_t s) {
-  if (!cross_shape_ok(B, T, S, H)) return -1;
+                      float* dvec, bf16_t* dq, bf16_t* dkv, const int* key_len, const uint8_t* mask, long msb,
+                      long msh, long mst, int B, int T, int S, int H, long ldq, long ldkv, float scale, float p_drop,
+                      uint64_t seed, hipStream_t s) {
+  if (!cross_shape_ok(B, T, S, H) || !cross_mask_ok(mask, msb, msh, mst, T, S)) return -1;
   AttnArgs p{};  // Dv = rowsum(dO * O) over the B*T query rows
   p.out = out; p.dout = dout; p.dvec = dvec; p.B = B; p.S = T; p.H = H;
   attn_bwd_prep_kernel<<<ca_cdiv((long)B * T * H, 32), 256, 0, s>>>(p);
@@ -1290,11 +1449,12 @@ int ca_attn_cross_bwd(const bf16_t* q, const bf16_t* kv, const bf16_t* out, cons
   a.q = q; a.kv = kv; a.dout = dout; a.lse = const_cast<float*>(lse); a.dvec = dvec; a.dq = dq; a.dkv = dkv;
   a.key_len = key_len; a.ldq = ldq; a.ldkv = ldkv;
   a.B = B; a.T = T; a.S = S; a.H = H; a.scale = scale; a.drop = make_drop(p_drop, seed);
-  if (cross_tail(a)) attn_cross_bwd_dkv_kernel<true><<<cross_kgrid(a), 256, 0, s>>>(a);
-  else attn_cross_bwd_dkv_kernel<false><<<cross_kgrid(a), 256, 0, s>>>(a);
+  cross_set_mask(a, mask, msb, msh, mst);
+  if (mask) launch_cross_bwd_dkv<true>(a, s);
+  else launch_cross_bwd_dkv<false>(a, s);
   CA_LAUNCH_CHECK();
-  if (cross_tail(a)) attn_cross_bwd_dq_kernel<true><<<cross_qgrid(a), 256, 0, s>>>(a);
-  else attn_cross_bwd_dq_kernel<false><<<cross_qgrid(a), 256, 0, s>>>(a);
+  if (mask) launch_cross_bwd_dq<true>(a, s);
+  else launch_cross_bwd_dq<false>(a, s);
   CA_LAUNCH_CHECK();
   return 0;
 }
