@@ -289,22 +289,23 @@ class BatchNormalization(Layer):
 
 
 class LayerNormalization(Layer):
-    def __init__(self, axis=-1, epsilon=1e-3, **kw):
+    def __init__(self, axis=-1, epsilon=1e-3, center=True, scale=True, **kw):
         super().__init__(**kw)
         self.epsilon = float(epsilon)
+        self.center, self.scale = bool(center), bool(scale)
 
     def build(self, input_shape):
         c = int(input_shape[-1])
-        self.gamma = torch.nn.Parameter(torch.ones(c))
-        self.beta = torch.nn.Parameter(torch.zeros(c))
+        # a disabled scale / offset creates no parameter (ops.layer_norm takes None for it)
+        self.gamma = torch.nn.Parameter(torch.ones(c)) if self.scale else None
+        self.beta = torch.nn.Parameter(torch.zeros(c)) if self.center else None
 
     def call(self, x, training=None):
-        y = F.layer_norm(x.float(), (x.shape[-1],), self.gamma, self.beta, self.epsilon)
-        return y.to(x.dtype)
+        return ops.layer_norm(x, self.gamma, self.beta, self.epsilon)
 
     def get_config(self):
         c = super().get_config()
-        c["epsilon"] = self.epsilon
+        c.update(epsilon=self.epsilon, center=self.center, scale=self.scale)
         return c
 
 

@@ -809,6 +809,80 @@ def ln_bwd(dy, h, mean, rstd, gamma, dgamma=None, dbeta=None, p_in=0.0, seed_in=
     return dh, dx
 
 
+def _ln_tuned(C, acts, params):
+    """The one dispatch rule of ``layer_norm_fwd`` / ``layer_norm_bwd``: the tuned one-wave-
+    per-row kernels of the BERT path (rowops.hip) take ``C % 4 == 0``, ``C <= 1344`` (their
+    backward's limit, so that both directions of one layer run in the same family) with every
+    activation pointer 8-byte aligned (they move 4 bf16 at a time; gamma / beta 4 floats: 16
+    bytes); the any-width kernels (layernorm.hip) take the rest."""
+    return (C % 4 == 0 and C <= 1344 and all(t is None or t.data_ptr() % 8 == 0 for t in acts)
+            and all(t.data_ptr() % 16 == 0 for t in params))
+
+
+def _ln_check(name, C, acts, params):
+    if not 1 <= C <= 16384:
+        raise ValueError(f"{name}: 1 <= C <= 16384 expected, got C = {C}")
+    for t in acts:
+        if t is not None and (t.dtype != torch.bfloat16 or not t.is_contiguous() or t.shape[-1] != C):
+            raise ValueError(f"{name}: contiguous bf16 [..., {C}] activations expected")
+    for t in params:
+        if t.dtype != torch.float32 or t.dim() != 1 or not t.is_contiguous():
+            raise ValueError(f"{name}: contiguous fp32 vectors expected for gamma / beta / mean / rstd")
+
+
+def layer_norm_fwd(x, gamma, beta, eps, residual=None):
+    """h = x (+ residual); y = LN(h) * gamma + beta over the last axis, for every
+    ``1 <= C <= 16384`` and any 2-byte-aligned bf16 ``x``.  Returns (y, h, mean, rstd): h is
+    None without a residual (it equals x); mean / rstd are the fp32 row statistics (two-pass).
+    See ``_ln_tuned`` for the kernel family that runs."""
+    ext = _ext.load(required=True)
+    C = x.shape[-1]
+    M = x.numel() // C
+    _ln_check("layer_norm_fwd", C, (x, residual), (gamma, beta))
+    if gamma.numel() != C or beta.numel() != C or (residual is not None and residual.shape != x.shape) or M < 1:
+        raise ValueError("layer_norm_fwd: gamma / beta [C], a residual of x's shape and at least one row expected")
+    if _ln_tuned(C, (x, residual), (gamma, beta)):
+        return ln_fwd(x, gamma, beta, eps, residual=residual)
+    y = torch.empty_like(x)
+    h = torch.empty_like(x) if residual is not None else None
+    mean = torch.empty(M, dtype=torch.float32, device=x.device)
+    rstd = torch.empty(M, dtype=torch.float32, device=x.device)
+    ext.layer_norm_fwd(x.data_ptr(), _ext.ptr(residual), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), _ext.ptr(h),
+                       mean.data_ptr(), rstd.data_ptr(), M, C, float(eps), _st(x.device))
+    return y, h, mean, rstd
+
+
+def layer_norm_bwd(dy, h, mean, rstd, gamma):
+    """Backward of ``layer_norm_fwd`` (``h``: its h, or x without a residual).  Returns
+    (dh, dgamma, dbeta): dh (bf16) is the gradient of x and of the residual; dgamma / dbeta
+    are fresh fp32 [C] tensors, summed from per-block partials in a fixed order (bitwise
+    reproducible).  Same dispatch rule as the forward."""
+    ext = _ext.load(required=True)
+    C = dy.shape[-1]
+    M = dy.numel() // C
+    _ln_check("layer_norm_bwd", C, (dy, h), (gamma, mean, rstd))
+    if gamma.numel() != C or h.shape != dy.shape or mean.numel() != M or rstd.numel() != M or M < 1:
+        raise ValueError("layer_norm_bwd: gamma [C], h of dy's shape and mean / rstd [rows] expected")
+    dgamma = torch.empty(C, dtype=torch.float32, device=dy.device)
+    dbeta = torch.empty(C, dtype=torch.float32, device=dy.device)
+    dh = torch.empty_like(dy)
+    # the gradients are returned to the caller (autograd), so they are finalised here, on
+    # this stream, also inside a ``deferred_finalize`` block
+    if _ln_tuned(C, (dy, h), (gamma,)):
+        ws = torch.empty(ext.ln_workspace_floats(M, C), dtype=torch.float32, device=dy.device)
+        ext.ln_bwd(dy.data_ptr(), h.data_ptr(), mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(), dh.data_ptr(), 0,
+                   dgamma.data_ptr(), dbeta.data_ptr(), 0, ws.data_ptr(), M, C, 0.0, 0, 0.0, 0, _st(dy.device))
+        return dh, dgamma, dbeta
+    parts = ext.layer_norm_bwd_parts(M, C)
+    ws = torch.empty(ext.layer_norm_bwd_workspace_floats(M, C), dtype=torch.float32, device=dy.device)
+    ext.layer_norm_bwd(dy.data_ptr(), h.data_ptr(), mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(), dh.data_ptr(),
+                       ws.data_ptr(), M, C, _st(dy.device))
+    fb = GradFinalizeBatch()
+    fb.add_cols(ws, parts, 2 * C, C, dgamma, dbeta, accumulate=False)
+    fb.flush()
+    return dh, dgamma, dbeta
+
+
 def cls_head_fwd(pooled, wc, bc, p_drop=0.0, seed=0):
     """logits[B, L] (fp32) = drop(pooled) @ wc^T + bc  (csrc/kernels/head.hip)."""
     ext = _ext.load(required=True)

@@ -108,6 +108,12 @@ int ca_ln_fwd(const bf16_t*, const bf16_t*, const float*, const float*, bf16_t*,
               float, float, uint64_t, float, uint64_t, const float*, hipStream_t);
 int ca_ln_bwd(const bf16_t*, const bf16_t*, const float*, const float*, const float*, bf16_t*, bf16_t*, float*, float*,
               int, float*, long, int, float, uint64_t, float, uint64_t, hipStream_t, float*);
+int ca_layer_norm_fwd(const bf16_t*, const bf16_t*, const float*, const float*, bf16_t*, bf16_t*, float*, float*, long,
+                      int, float, hipStream_t);
+long ca_layer_norm_bwd_parts(long, int);
+long ca_layer_norm_bwd_workspace_floats(long, int);
+int ca_layer_norm_bwd(const bf16_t*, const bf16_t*, const float*, const float*, const float*, bf16_t*, float*, long, int,
+                      hipStream_t);
 long ca_colsum_workspace_floats(long, int);
 int ca_colsum(const bf16_t*, long, int, long, float*, int, float*, hipStream_t);
 int ca_act_grad(const bf16_t*, long, int, const bf16_t*, bf16_t*, long, int, int, hipStream_t);
@@ -467,6 +473,18 @@ PYBIND11_MODULE(_C, m) {
   }, py::arg("dy"), py::arg("h"), py::arg("mu"), py::arg("rs"), py::arg("g"), py::arg("dh"), py::arg("dx"),
         py::arg("dg"), py::arg("db"), py::arg("acc"), py::arg("ws"), py::arg("M"), py::arg("C"), py::arg("p_in"),
         py::arg("seed_in"), py::arg("p_out"), py::arg("seed_out"), py::arg("s"), py::arg("dsum") = 0);
+  m.def("layer_norm_fwd", [](u64 x, u64 res, u64 g, u64 b, u64 y, u64 h, u64 mu, u64 rs, long M, int C, float eps,
+                             u64 s) {
+    check(ca_layer_norm_fwd(P(const bf16_t*, x), P(const bf16_t*, res), P(const float*, g), P(const float*, b),
+                            P(bf16_t*, y), P(bf16_t*, h), P(float*, mu), P(float*, rs), M, C, eps, S(s)),
+          "layer_norm_fwd");
+  });
+  m.def("layer_norm_bwd_parts", [](long M, int C) { return ca_layer_norm_bwd_parts(M, C); });
+  m.def("layer_norm_bwd_workspace_floats", [](long M, int C) { return ca_layer_norm_bwd_workspace_floats(M, C); });
+  m.def("layer_norm_bwd", [](u64 dy, u64 h, u64 mu, u64 rs, u64 g, u64 dh, u64 ws, long M, int C, u64 s) {
+    check(ca_layer_norm_bwd(P(const bf16_t*, dy), P(const bf16_t*, h), P(const float*, mu), P(const float*, rs),
+                            P(const float*, g), P(bf16_t*, dh), P(float*, ws), M, C, S(s)), "layer_norm_bwd");
+  });
   m.def("pad_cols", [](u64 in, long ld, int cols, u64 out, int cols_out, long rows, long rows_out, int eb, u64 s) {
     check(ca_pad_cols(P(const void*, in), ld, cols, P(void*, out), cols_out, rows, rows_out, eb, S(s)), "pad_cols");
   });
