@@ -19,14 +19,18 @@
 // MFMA: v_mfma_f32_16x16x32_bf16; K-contiguous operands via ds_read_b128,
 // N-contiguous ones (V / dO / Q / K as B with k along rows) via ds_read_b64_tr_b16.
 //
-// Shapes: any S; S = 64 / 128 take the one-workgroup kernels (below), every other S the
-// generic ones on ceil(S / 64) blocks.  S % 64 != 0 runs their TAIL instantiation, which only
-// masks: fragment rows >= S are clamped to row S - 1, tile rows >= S are zero-filled in LDS,
-// lse / Dv of queries >= S are not read (dKV: p = dS = 0 for those columns), and only rows
-// < S are stored.  The non-tail instantiation is the code that ran before the split.
+// Kernels: one generic family (forward, dK/dV, dQ; templates on TAIL, MASK, CAUSAL; see GenArgs)
+// that serves self-attention on the packed qkv and cross-attention on separate q and kv, two
+// one-workgroup kernels for self-attention at S = 64 / 128 (below), and the prep kernel.
 //
-// Causal mode (CAUSAL, a compile-time parameter of all six kernels; the non-causal
-// instantiations are the code without it): key j is visible to query i iff j <= i and
+// Shapes: any S; self-attention at S = 64 / 128 takes the one-workgroup kernels, every other
+// call the generic ones on ceil(S / 64) blocks.  S % 64 != 0 runs their TAIL instantiation, which
+// only masks: fragment rows >= S are clamped to row S - 1, tile rows >= S are zero-filled in LDS,
+// lse / Dv of queries >= S are not read (dKV: p = dS = 0 for those columns), and only rows
+// < S are stored.
+//
+// Causal mode (CAUSAL, a compile-time parameter of the generic and the one-workgroup kernels; the
+// non-causal instantiations are the code without it): key j is visible to query i iff j <= i and
 // j < key_len[b], so key 0 is visible to every query and no row is fully masked.  The generic
 // kernels skip the 64x64 blocks that lie entirely in the future -- forward and dQ stop after the
 // diagonal key block, dK/dV starts at the diagonal query block, all bounds workgroup-uniform --
@@ -37,9 +41,9 @@
 // dropout element index is the same in both modes.
 //
 // Cross-attention (queries and keys / values in separate tensors, own lengths and row pitches)
-// has three generic kernels of its own below the self-attention ones: see CrossArgs.  They also
-// take an arbitrary byte mask (MASK, a compile-time parameter like TAIL), which is how masked
-// self-attention runs: on the Q and K | V column views of the packed qkv.
+// runs on the generic kernels as well: see GenArgs.  They also take an arbitrary byte mask (MASK,
+// a compile-time parameter like TAIL), non-causal only; masked self-attention comes in through the
+// cross-attention entry points, on the Q and K | V column views of the packed qkv.
 #include "ca_mfma_core.h"
 #include "ca_rng.h"
 
@@ -131,6 +135,7 @@ __device__ __forceinline__ int block_x() {
   return (int)blockIdx.x;
 }
 
+// Arguments of the one-workgroup kernels and of the prep kernel (the generic kernels take GenArgs)
 struct AttnArgs {
   const bf16_t* qkv;   // [B*S][3*H*D]
   const bf16_t* out;   // ctx [B*S][H*D] (bwd: O)
@@ -144,139 +149,6 @@ struct AttnArgs {
   float scale;
   DropCfg drop;
 };
-
-template <bool TAIL, bool CAUSAL>
-__global__ void __launch_bounds__(256) attn_fwd_kernel(AttnArgs a) {
-  __shared__ __attribute__((aligned(16))) short Ks[KB * LDT];
-  __shared__ __attribute__((aligned(16))) short Vs[KB * LDT];
-  __shared__ __attribute__((aligned(16))) short Ps[4][16 * PLD];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int b = blockIdx.z, h = blockIdx.y;
-  const int bx = block_x<CAUSAL>();
-  const int S = a.S, H = a.H, C = H * D;
-  const long ldq = 3L * C;
-  const int q0 = bx * QB + wave * 16;
-  int klen = a.key_len ? a.key_len[b] : S;
-  klen = klen < 1 ? 1 : (klen > S ? S : klen);
-  const bf16_t* base = a.qkv + (long)b * S * ldq;
-  const bf16_t* qrow = base + (long)frag_row<TAIL>(q0 + (lane & 15), S) * ldq + h * D;
-  const bf16x8 qf0 = gfrag(qrow, 0, lane), qf1 = gfrag(qrow, 1, lane);
-  const float c2 = a.scale * LOG2E;
-  const long bh = (long)b * H + h;
-  const uint64_t bhss = (uint64_t)bh * S * S;  // dropout index of element (q, key): bhss + q*S + key
-
-  f4v o[4];
-  // causal: lr = the row sum of the probabilities as the P V product sees them (rounded to bf16).
-  // The context is divided by lr, so its weights sum to one exactly; the log-sum-exp keeps the
-  // unrounded sum l, which is what the backward recomputes P from.  A causal row has as few as one
-  // or two visible keys, where dS = P (dP - Dv) nearly cancels and Dv = rowsum(dO * ctx) must not
-  // carry the weights' rounding as an absolute error: dividing by l left 2.0e-2 on a dK block at
-  // S = 2 where dividing by lr leaves 7.6e-3.  The non-causal kernels divide by l as before.
-  float m[4], l[4], lr[4];
-#pragma unroll
-  for (int t = 0; t < 4; ++t) o[t] = f4v{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    m[r] = -INFINITY;
-    l[r] = lr[r] = 0.f;
-  }
-  short* slab = Ps[wave];
-  int nkb = (klen + KB - 1) / KB;
-  // causal: key blocks past the diagonal one (QB == KB) are entirely in the future
-  if constexpr (CAUSAL) nkb = nkb < bx + 1 ? nkb : bx + 1;
-  for (int kb = 0; kb < nkb; ++kb) {
-    const int k0 = kb * KB;
-    __syncthreads();
-    tile_load<TAIL>(Ks, base + (long)k0 * ldq + C + h * D, ldq, tid, S - k0);
-    tile_load<TAIL>(Vs, base + (long)k0 * ldq + 2 * C + h * D, ldq, tid, S - k0);
-    __syncthreads();
-    const bool diag = CAUSAL && kb == bx;  // the only block that needs key <= q
-    f4v s[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      s[t] = f4v{0.f, 0.f, 0.f, 0.f};
-      s[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf0, read_frag<64, true>(Ks, t * 16, 0, lane), s[t], 0, 0, 0);
-      s[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf1, read_frag<64, true>(Ks, t * 16, 32, lane), s[t], 0, 0, 0);
-    }
-    float alpha[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      float mx = -INFINITY;
-      int kend = klen;  // first masked key of this row
-      if constexpr (CAUSAL) {
-        const int q = q0 + (lane >> 4) * 4 + r;
-        kend = (diag && q + 1 < klen) ? q + 1 : klen;
-      }
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const int key = k0 + t * 16 + (lane & 15);
-        const float v = key < kend ? s[t][r] * c2 : -INFINITY;
-        s[t][r] = v;
-        mx = fmaxf(mx, v);
-      }
-      mx = grp16_max(mx);
-      const float mn = fmaxf(m[r], mx);
-      alpha[r] = exp2f(m[r] - mn);
-      m[r] = mn;
-      float ls = 0.f, lsr = 0.f;
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const float p = exp2f(s[t][r] - mn);
-        ls += p;
-        if constexpr (CAUSAL) lsr += bf2f(f2bf(p));
-        s[t][r] = p;
-      }
-      l[r] = l[r] * alpha[r] + ls;
-      if constexpr (CAUSAL) lr[r] = lr[r] * alpha[r] + lsr;
-    }
-    if (a.drop.on) {
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int q = q0 + (lane >> 4) * 4 + r;
-          const int key = k0 + t * 16 + (lane & 15);
-          s[t][r] *= drop_mul(a.drop, bhss + (uint32_t)(q * S + key));
-        }
-    }
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) o[t][r] *= alpha[r];
-    slab_store(slab, s, lane);
-    __builtin_amdgcn_wave_barrier();
-    const bf16x8 p0 = slab_frag(slab, 0, lane), p1 = slab_frag(slab, 1, lane);
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      o[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(p0, read_frag<64, false>(Vs, t * 16, 0, lane), o[t], 0, 0, 0);
-      o[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(p1, read_frag<64, false>(Vs, t * 16, 32, lane), o[t], 0, 0, 0);
-    }
-    __builtin_amdgcn_wave_barrier();
-  }
-  float inv[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const float lt = grp16_sum(l[r]);
-    inv[r] = 1.f / (CAUSAL ? grp16_sum(lr[r]) : lt);
-    if ((lane & 15) == 0 && (!TAIL || q0 + (lane >> 4) * 4 + r < S))
-      a.lse[bh * S + q0 + (lane >> 4) * 4 + r] = m[r] + log2f(lt);
-  }
-  // normalise, stage through the wave slab, 16-B row stores
-#pragma unroll
-  for (int t = 0; t < 4; ++t)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) o[t][r] *= inv[r];
-  slab_store(slab, o, lane);
-  __builtin_amdgcn_wave_barrier();
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int c = lane + i * 64;  // 16 rows x 8 chunks
-    const int r = c >> 3, col = (c & 7) * 8;
-    if (!TAIL || q0 + r < S)
-      *reinterpret_cast<s8v*>(a.ctx + ((long)b * S + q0 + r) * C + h * D + col) =
-          *reinterpret_cast<const s8v*>(slab + r * PLD + col);
-  }
-}
 
 // Dv[b,h,q] = sum_d dO[q, h*D+d] * O[q, h*D+d]: 8 lanes x 8 elements per (row, head)
 __global__ void __launch_bounds__(256) attn_bwd_prep_kernel(AttnArgs a) {
@@ -302,219 +174,14 @@ __global__ void __launch_bounds__(256) attn_bwd_prep_kernel(AttnArgs a) {
   }
 }
 
-template <bool TAIL, bool CAUSAL>
-__global__ void __launch_bounds__(256) attn_bwd_dkv_kernel(AttnArgs a) {
-  __shared__ __attribute__((aligned(16))) short Qs[QB * LDT];
-  __shared__ __attribute__((aligned(16))) short Gs[QB * LDT];  // dO
-  __shared__ __attribute__((aligned(16))) short Ps[4][16 * PLD];
-  __shared__ __attribute__((aligned(16))) short Ds[4][16 * PLD];
-  __shared__ float lse_s[QB], dv_s[QB];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int b = blockIdx.z, h = blockIdx.y;
-  const int bx = block_x<CAUSAL>();
-  const int S = a.S, H = a.H, C = H * D;
-  const long ldq = 3L * C;
-  const int k0 = bx * KB + wave * 16;  // this wave's 16 keys
-  int klen = a.key_len ? a.key_len[b] : S;
-  klen = klen < 1 ? 1 : (klen > S ? S : klen);
-  const long bh = (long)b * H + h;
-  const uint64_t bhss = (uint64_t)bh * S * S;  // dropout index of element (q, key): bhss + q*S + key
-  const bf16_t* base = a.qkv + (long)b * S * ldq;
-  const int frow = frag_row<TAIL>(k0 + (lane & 15), S);
-  const bf16_t* krow = base + (long)frow * ldq + C + h * D;
-  const bf16_t* vrow = base + (long)frow * ldq + 2 * C + h * D;
-  const bf16x8 kf0 = gfrag(krow, 0, lane), kf1 = gfrag(krow, 1, lane);
-  const bf16x8 vf0 = gfrag(vrow, 0, lane), vf1 = gfrag(vrow, 1, lane);
-  const float c2 = a.scale * LOG2E;
-  f4v dk[4], dv[4];
-#pragma unroll
-  for (int t = 0; t < 4; ++t) dk[t] = dv[t] = f4v{0.f, 0.f, 0.f, 0.f};
-  short* pslab = Ps[wave];
-  short* dslab = Ds[wave];
-  const bool any_valid = (uint32_t)bx * KB < (uint32_t)klen;
-  const int nqb = any_valid ? (TAIL ? (S + QB - 1) / QB : S / QB) : 0;
-  // causal: query blocks before the diagonal one (QB == KB) see none of this block's keys
-  for (int qb = CAUSAL ? bx : 0; qb < nqb; ++qb) {
-    const int q0 = qb * QB;
-    const bool diag = CAUSAL && qb == bx;  // the only block that needs key <= q
-    __syncthreads();
-    tile_load<TAIL>(Qs, base + (long)q0 * ldq + h * D, ldq, tid, S - q0);
-    tile_load<TAIL>(Gs, a.dout + ((long)b * S + q0) * C + h * D, C, tid, S - q0);
-    if (tid < QB) {
-      const bool live = !TAIL || q0 + tid < S;  // queries >= S: no lse / Dv entry exists
-      lse_s[tid] = live ? a.lse[bh * S + q0 + tid] : 0.f;
-      dv_s[tid] = live ? a.dvec[bh * S + q0 + tid] : 0.f;
-    }
-    __syncthreads();
-    // S^T: rows = keys (this wave), cols = queries
-    f4v p[4], dp[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      p[t] = f4v{0.f, 0.f, 0.f, 0.f};
-      p[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf0, read_frag<64, true>(Qs, t * 16, 0, lane), p[t], 0, 0, 0);
-      p[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf1, read_frag<64, true>(Qs, t * 16, 32, lane), p[t], 0, 0, 0);
-      dp[t] = f4v{0.f, 0.f, 0.f, 0.f};
-      dp[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf0, read_frag<64, true>(Gs, t * 16, 0, lane), dp[t], 0, 0, 0);
-      dp[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf1, read_frag<64, true>(Gs, t * 16, 32, lane), dp[t], 0, 0, 0);
-    }
-    f4v pd[4], ds[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const int qi = t * 16 + (lane & 15);
-      const float ls = lse_s[qi], dvq = dv_s[qi];
-      const bool qlive = !TAIL || q0 + qi < S;  // a query column >= S adds p = dS = 0
-      int kend = klen;  // first masked key of this query column
-      if constexpr (CAUSAL) kend = (diag && q0 + qi + 1 < klen) ? q0 + qi + 1 : klen;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int key = k0 + (lane >> 4) * 4 + r;
-        const float pr = (key < kend && qlive) ? exp2f(p[t][r] * c2 - ls) : 0.f;
-        const float mul = a.drop.on ? drop_mul(a.drop, bhss + (uint32_t)((q0 + qi) * S + key)) : 1.f;
-        pd[t][r] = pr * mul;
-        ds[t][r] = pr * (dp[t][r] * mul - dvq);
-      }
-    }
-    slab_store(pslab, pd, lane);
-    slab_store(dslab, ds, lane);
-    __builtin_amdgcn_wave_barrier();
-    const bf16x8 pa0 = slab_frag(pslab, 0, lane), pa1 = slab_frag(pslab, 1, lane);
-    const bf16x8 da0 = slab_frag(dslab, 0, lane), da1 = slab_frag(dslab, 1, lane);
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      dv[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pa0, read_frag<64, false>(Gs, t * 16, 0, lane), dv[t], 0, 0, 0);
-      dv[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pa1, read_frag<64, false>(Gs, t * 16, 32, lane), dv[t], 0, 0, 0);
-      dk[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(da0, read_frag<64, false>(Qs, t * 16, 0, lane), dk[t], 0, 0, 0);
-      dk[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(da1, read_frag<64, false>(Qs, t * 16, 32, lane), dk[t], 0, 0, 0);
-    }
-    __builtin_amdgcn_wave_barrier();
-  }
-#pragma unroll
-  for (int t = 0; t < 4; ++t)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) dk[t][r] *= a.scale;
-  // stage through the slabs -> 16-B stores into dqkv (K and V thirds)
-  slab_store(pslab, dk, lane);
-  slab_store(dslab, dv, lane);
-  __builtin_amdgcn_wave_barrier();
-  bf16_t* drow = a.dqkv + ((long)b * S + k0) * ldq;
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int c = lane + i * 64;
-    const int r = c >> 3, col = (c & 7) * 8;
-    if (!TAIL || k0 + r < S) {
-      *reinterpret_cast<s8v*>(drow + (long)r * ldq + C + h * D + col) =
-          *reinterpret_cast<const s8v*>(pslab + r * PLD + col);
-      *reinterpret_cast<s8v*>(drow + (long)r * ldq + 2 * C + h * D + col) =
-          *reinterpret_cast<const s8v*>(dslab + r * PLD + col);
-    }
-  }
-}
-
-// (the tail variant's few extra index registers would cost the third wave per SIMD that the
-// non-tail one gets unasked: 174 against 168 registers; "1" is the default)
-// Causal, non-tail: the diagonal test takes it to 141 + 32 = 173 registers and two waves when left
-// alone; asked for three it fits in 160 without scratch, like the tail variants (154).
-#define DQ_WAVES(TAIL, CAUSAL) (((TAIL) || (CAUSAL)) ? 3 : 1)
-template <bool TAIL, bool CAUSAL>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DQ_WAVES(TAIL, CAUSAL))))
-attn_bwd_dq_kernel(AttnArgs a) {
-  __shared__ __attribute__((aligned(16))) short Ks[KB * LDT];
-  __shared__ __attribute__((aligned(16))) short Vs[KB * LDT];
-  __shared__ __attribute__((aligned(16))) short Ds[4][16 * PLD];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int b = blockIdx.z, h = blockIdx.y;
-  const int bx = block_x<CAUSAL>();
-  const int S = a.S, H = a.H, C = H * D;
-  const long ldq = 3L * C;
-  const int q0 = bx * QB + wave * 16;
-  int klen = a.key_len ? a.key_len[b] : S;
-  klen = klen < 1 ? 1 : (klen > S ? S : klen);
-  const long bh = (long)b * H + h;
-  const uint64_t bhss = (uint64_t)bh * S * S;  // dropout index of element (q, key): bhss + q*S + key
-  const bf16_t* base = a.qkv + (long)b * S * ldq;
-  const bf16_t* qrow = base + (long)frag_row<TAIL>(q0 + (lane & 15), S) * ldq + h * D;
-  const bf16_t* grow = a.dout + ((long)b * S + q0 + (lane & 15)) * C + h * D;
-  if constexpr (TAIL) grow = a.dout + ((long)b * S + frag_row<TAIL>(q0 + (lane & 15), S)) * C + h * D;
-  const bf16x8 qf0 = gfrag(qrow, 0, lane), qf1 = gfrag(qrow, 1, lane);
-  const bf16x8 gf0 = gfrag(grow, 0, lane), gf1 = gfrag(grow, 1, lane);
-  const float c2 = a.scale * LOG2E;
-  float ls[4], dvq[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int q = frag_row<TAIL>(q0 + (lane >> 4) * 4 + r, S);
-    ls[r] = a.lse[bh * S + q];
-    dvq[r] = a.dvec[bh * S + q];
-  }
-  f4v dq[4];
-#pragma unroll
-  for (int t = 0; t < 4; ++t) dq[t] = f4v{0.f, 0.f, 0.f, 0.f};
-  short* dslab = Ds[wave];
-  int nkb = (klen + KB - 1) / KB;
-  // causal: key blocks past the diagonal one (QB == KB) are entirely in the future
-  if constexpr (CAUSAL) nkb = nkb < bx + 1 ? nkb : bx + 1;
-  for (int kb = 0; kb < nkb; ++kb) {
-    const int k0 = kb * KB;
-    __syncthreads();
-    tile_load<TAIL>(Ks, base + (long)k0 * ldq + C + h * D, ldq, tid, S - k0);
-    tile_load<TAIL>(Vs, base + (long)k0 * ldq + 2 * C + h * D, ldq, tid, S - k0);
-    __syncthreads();
-    const bool diag = CAUSAL && kb == bx;  // the only block that needs key <= q
-    f4v s[4], dp[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      s[t] = f4v{0.f, 0.f, 0.f, 0.f};
-      s[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf0, read_frag<64, true>(Ks, t * 16, 0, lane), s[t], 0, 0, 0);
-      s[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf1, read_frag<64, true>(Ks, t * 16, 32, lane), s[t], 0, 0, 0);
-      dp[t] = f4v{0.f, 0.f, 0.f, 0.f};
-      dp[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(gf0, read_frag<64, true>(Vs, t * 16, 0, lane), dp[t], 0, 0, 0);
-      dp[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(gf1, read_frag<64, true>(Vs, t * 16, 32, lane), dp[t], 0, 0, 0);
-    }
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const int key = k0 + t * 16 + (lane & 15);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int q = q0 + (lane >> 4) * 4 + r;
-        bool vis = key < klen;
-        if constexpr (CAUSAL) vis = vis && (!diag || key <= q);
-        const float pr = vis ? exp2f(s[t][r] * c2 - ls[r]) : 0.f;
-        const float mul = a.drop.on ? drop_mul(a.drop, bhss + (uint32_t)(q * S + key)) : 1.f;
-        s[t][r] = pr * (dp[t][r] * mul - dvq[r]);
-      }
-    }
-    slab_store(dslab, s, lane);
-    __builtin_amdgcn_wave_barrier();
-    const bf16x8 d0 = slab_frag(dslab, 0, lane), d1 = slab_frag(dslab, 1, lane);
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      dq[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(d0, read_frag<64, false>(Ks, t * 16, 0, lane), dq[t], 0, 0, 0);
-      dq[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(d1, read_frag<64, false>(Ks, t * 16, 32, lane), dq[t], 0, 0, 0);
-    }
-    __builtin_amdgcn_wave_barrier();
-  }
-#pragma unroll
-  for (int t = 0; t < 4; ++t)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) dq[t][r] *= a.scale;
-  slab_store(dslab, dq, lane);
-  __builtin_amdgcn_wave_barrier();
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int c = lane + i * 64;
-    const int r = c >> 3, col = (c & 7) * 8;
-    if (!TAIL || q0 + r < S)
-      *reinterpret_cast<s8v*>(a.dqkv + ((long)b * S + q0 + r) * ldq + h * D + col) =
-          *reinterpret_cast<const s8v*>(dslab + r * PLD + col);
-  }
-}
-
 // ---------------------------------------------------------------------------
-// Cross-attention: T queries q[B*T][H*D] (row pitch ldq) against S keys / values packed as
-// kv[B*S][2*H*D] (K | V, row pitch ldkv), T and S independent, non-causal.  The three kernels are
-// the non-causal generic ones above with the query rows and the key / value rows taken apart:
-// the same block loops, arithmetic and operation order, so with T == S, q = qkv[:, :C] and
-// kv = qkv[:, C:] (both at pitch 3C) they store what those store, bit for bit.  Forward and dQ run
-// on ceil(T / 64) query blocks and loop over the key blocks below key_len; dK/dV runs on
+// The generic kernels <TAIL, MASK, CAUSAL>: T queries q[B*T][H*D] (row pitch ldq) against S keys /
+// values packed as kv[B*S][2*H*D] (K | V, row pitch ldkv), gradients to dq (pitch lddq) and dkv
+// (K | V, pitch lddkv).  Cross-attention passes two tensors, T and S independent, and contiguous
+// gradients (lddq = C, lddkv = 2C).  Self-attention passes the column ranges of the packed
+// projection: q = qkv, kv = qkv + C, dq = dqkv, dkv = dqkv + C, every pitch 3C, T == S.  Both run
+// the same instantiation, so they store the same bits on the same rows.  Forward and dQ run on
+// ceil(T / 64) query blocks and loop over the key blocks below key_len; dK/dV runs on
 // ceil(S / 64) key blocks and loops over the query blocks.  TAIL = T or S is not a multiple of
 // 64: every clamp, zero fill, lse / Dv guard and store guard uses the length of the tensor its
 // rows come from.  The dropout element index is (b*H + h)*T*S + q*S + key.
@@ -524,19 +191,22 @@ attn_bwd_dq_kernel(AttnArgs a) {
 // blocks at or past key_len are still not read.  A query that sees no key is possible then: its
 // context is exactly 0, its lse is stored as 0, and it adds exactly 0 to dQ, dK and dV (the
 // backward selects p = 0 for a hidden element, it never multiplies by a masked exp2f); a key no
-// query sees gets exact-zero dK / dV rows.  Every statement of it is under if constexpr (MASK):
-// the MASK = false instantiations are the kernels as they were.
-struct CrossArgs {
+// query sees gets exact-zero dK / dV rows.
+//
+// CAUSAL (needs T == S; the self-attention entry points are its only callers): see the header.
+// Every statement of MASK and of CAUSAL is under its if constexpr, and the two are not combined:
+// a masked causal call ANDs the triangle into its mask before it gets here.
+struct GenArgs {
   const bf16_t* q;     // [B*T] rows of H*D, pitch ldq
   const bf16_t* kv;    // [B*S] rows of 2*H*D, pitch ldkv
   const bf16_t* dout;  // dctx [B*T][H*D] (bwd)
   bf16_t* ctx;         // fwd output [B*T][H*D]
-  bf16_t* dq;          // bwd output [B*T][H*D]
-  bf16_t* dkv;         // bwd output [B*S][2*H*D]
+  bf16_t* dq;          // bwd output [B*T] rows of H*D, pitch lddq
+  bf16_t* dkv;         // bwd output [B*S] rows of 2*H*D, pitch lddkv
   float* lse;          // [B][H][T] (log2 domain)
   float* dvec;         // [B][H][T] rowsum(dO*O)
   const int* key_len;  // [B] or null
-  long ldq, ldkv;
+  long ldq, ldkv, lddq, lddkv;
   int B, T, S, H;
   float scale;
   DropCfg drop;
@@ -631,13 +301,15 @@ __device__ __forceinline__ uint32_t mask_pack_k(const MaskRaw& m, int lane) {
   return bits;
 }
 
-template <bool TAIL, bool MASK>
-__global__ void __launch_bounds__(256) attn_cross_fwd_kernel(CrossArgs a) {
+template <bool TAIL, bool MASK, bool CAUSAL>
+__global__ void __launch_bounds__(256) attn_fwd_kernel(GenArgs a) {
+  static_assert(!(MASK && CAUSAL), "a masked causal call carries the triangle in its mask");
   __shared__ __attribute__((aligned(16))) short Ks[KB * LDT];
   __shared__ __attribute__((aligned(16))) short Vs[KB * LDT];
   __shared__ __attribute__((aligned(16))) short Ps[4][16 * PLD];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int b = blockIdx.z, h = blockIdx.y, bx = blockIdx.x;
+  const int b = blockIdx.z, h = blockIdx.y;
+  const int bx = block_x<CAUSAL>();
   const int T = a.T, S = a.S, H = a.H, C = H * D;
   const long ldkv = a.ldkv;
   const int q0 = bx * QB + wave * 16;
@@ -653,16 +325,24 @@ __global__ void __launch_bounds__(256) attn_cross_fwd_kernel(CrossArgs a) {
   if constexpr (MASK) mb = a.mask + b * a.msb + h * a.msh;
 
   f4v o[4];
-  float m[4], l[4];
+  // causal: lr = the row sum of the probabilities as the P V product sees them (rounded to bf16).
+  // The context is divided by lr, so its weights sum to one exactly; the log-sum-exp keeps the
+  // unrounded sum l, which is what the backward recomputes P from.  A causal row has as few as one
+  // or two visible keys, where dS = P (dP - Dv) nearly cancels and Dv = rowsum(dO * ctx) must not
+  // carry the weights' rounding as an absolute error: dividing by l left 2.0e-2 on a dK block at
+  // S = 2 where dividing by lr leaves 7.6e-3.  The non-causal kernels divide by l.
+  float m[4], l[4], lr[4];
 #pragma unroll
   for (int t = 0; t < 4; ++t) o[t] = f4v{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     m[r] = -INFINITY;
-    l[r] = 0.f;
+    l[r] = lr[r] = 0.f;
   }
   short* slab = Ps[wave];
-  const int nkb = (klen + KB - 1) / KB;  // key blocks entirely past key_len are not read
+  int nkb = (klen + KB - 1) / KB;  // key blocks entirely past key_len are not read
+  // causal: key blocks past the diagonal one (QB == KB) are entirely in the future
+  if constexpr (CAUSAL) nkb = nkb < bx + 1 ? nkb : bx + 1;
   for (int kb = 0; kb < nkb; ++kb) {
     const int k0 = kb * KB;
     MaskRaw mraw;
@@ -673,6 +353,7 @@ __global__ void __launch_bounds__(256) attn_cross_fwd_kernel(CrossArgs a) {
     uint32_t vis = 0;
     if constexpr (MASK) vis = mask_pack_q(mraw);  // here: the mask bytes arrive before the tile's
     __syncthreads();
+    const bool diag = CAUSAL && kb == bx;  // the only block that needs key <= q
     f4v s[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
@@ -684,10 +365,15 @@ __global__ void __launch_bounds__(256) attn_cross_fwd_kernel(CrossArgs a) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       float mx = -INFINITY;
+      int kend = klen;  // first masked key of this row
+      if constexpr (CAUSAL) {
+        const int q = q0 + (lane >> 4) * 4 + r;
+        kend = (diag && q + 1 < klen) ? q + 1 : klen;
+      }
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
         const int key = k0 + t * 16 + (lane & 15);
-        bool seen = key < klen;
+        bool seen = key < kend;
         if constexpr (MASK) seen = seen && ((vis >> (4 * t + r)) & 1u);
         const float v = seen ? s[t][r] * c2 : -INFINITY;
         s[t][r] = v;
@@ -701,14 +387,16 @@ __global__ void __launch_bounds__(256) attn_cross_fwd_kernel(CrossArgs a) {
       if constexpr (MASK) ms = mn == -INFINITY ? 0.f : mn;
       alpha[r] = exp2f(m[r] - ms);
       m[r] = mn;
-      float ls = 0.f;
+      float ls = 0.f, lsr = 0.f;
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
         const float p = exp2f(s[t][r] - ms);
         ls += p;
+        if constexpr (CAUSAL) lsr += bf2f(f2bf(p));
         s[t][r] = p;
       }
       l[r] = l[r] * alpha[r] + ls;
+      if constexpr (CAUSAL) lr[r] = lr[r] * alpha[r] + lsr;
     }
     if (a.drop.on) {
 #pragma unroll
@@ -738,13 +426,13 @@ __global__ void __launch_bounds__(256) attn_cross_fwd_kernel(CrossArgs a) {
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const float lt = grp16_sum(l[r]);
-    inv[r] = 1.f / lt;
-    float lr = m[r] + log2f(lt);
+    inv[r] = 1.f / (CAUSAL ? grp16_sum(lr[r]) : lt);
+    float lse = m[r] + log2f(lt);
     if constexpr (MASK) {  // a row with no visible key: context 0, lse 0 (the backward selects p = 0)
       inv[r] = lt > 0.f ? inv[r] : 0.f;
-      lr = lt > 0.f ? lr : 0.f;
+      lse = lt > 0.f ? lse : 0.f;
     }
-    if ((lane & 15) == 0 && (!TAIL || q0 + (lane >> 4) * 4 + r < T)) a.lse[bh * T + q0 + (lane >> 4) * 4 + r] = lr;
+    if ((lane & 15) == 0 && (!TAIL || q0 + (lane >> 4) * 4 + r < T)) a.lse[bh * T + q0 + (lane >> 4) * 4 + r] = lse;
   }
   // normalise, stage through the wave slab, 16-B row stores
 #pragma unroll
@@ -764,17 +452,19 @@ __global__ void __launch_bounds__(256) attn_cross_fwd_kernel(CrossArgs a) {
 }
 
 // grid: ceil(S / 64) key blocks; rows of keys >= key_len[b] are stored as exact zeros
-template <bool TAIL, bool MASK>
-__global__ void __launch_bounds__(256) attn_cross_bwd_dkv_kernel(CrossArgs a) {
+template <bool TAIL, bool MASK, bool CAUSAL>
+__global__ void __launch_bounds__(256) attn_bwd_dkv_kernel(GenArgs a) {
+  static_assert(!(MASK && CAUSAL), "a masked causal call carries the triangle in its mask");
   __shared__ __attribute__((aligned(16))) short Qs[QB * LDT];
   __shared__ __attribute__((aligned(16))) short Gs[QB * LDT];  // dO
   __shared__ __attribute__((aligned(16))) short Ps[4][16 * PLD];
   __shared__ __attribute__((aligned(16))) short Ds[4][16 * PLD];
   __shared__ float lse_s[QB], dv_s[QB];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int b = blockIdx.z, h = blockIdx.y, bx = blockIdx.x;
+  const int b = blockIdx.z, h = blockIdx.y;
+  const int bx = block_x<CAUSAL>();
   const int T = a.T, S = a.S, H = a.H, C = H * D;
-  const long ldq = a.ldq, ldkv = a.ldkv;
+  const long ldq = a.ldq, ldkv = a.ldkv, lddkv = a.lddkv;
   const int k0 = bx * KB + wave * 16;  // this wave's 16 keys
   int klen = a.key_len ? a.key_len[b] : S;
   klen = klen < 1 ? 1 : (klen > S ? S : klen);
@@ -796,8 +486,10 @@ __global__ void __launch_bounds__(256) attn_cross_bwd_dkv_kernel(CrossArgs a) {
   const int nqb = any_valid ? (T + QB - 1) / QB : 0;
   const uint8_t* mb = nullptr;
   if constexpr (MASK) mb = a.mask + b * a.msb + h * a.msh;
-  for (int qb = 0; qb < nqb; ++qb) {
+  // causal: query blocks before the diagonal one (QB == KB) see none of this block's keys
+  for (int qb = CAUSAL ? bx : 0; qb < nqb; ++qb) {
     const int q0 = qb * QB;
+    const bool diag = CAUSAL && qb == bx;  // the only block that needs key <= q
     MaskRaw mraw;
     if constexpr (MASK) mraw = mask_load_k<TAIL>(mb, (uint32_t)a.mst, q0, k0, T, S, lane);
     __syncthreads();
@@ -828,10 +520,12 @@ __global__ void __launch_bounds__(256) attn_cross_bwd_dkv_kernel(CrossArgs a) {
       const int qi = t * 16 + (lane & 15);
       const float ls = lse_s[qi], dvq = dv_s[qi];
       const bool qlive = !TAIL || q0 + qi < T;  // a query column >= T adds p = dS = 0
+      int kend = klen;  // first masked key of this query column
+      if constexpr (CAUSAL) kend = (diag && q0 + qi + 1 < klen) ? q0 + qi + 1 : klen;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int key = k0 + (lane >> 4) * 4 + r;
-        bool seen = key < klen && qlive;
+        bool seen = key < kend && qlive;
         if constexpr (MASK) seen = seen && ((vis >> (4 * t + r)) & 1u);
         const float pr = seen ? exp2f(p[t][r] * c2 - ls) : 0.f;
         const float mul =
@@ -862,27 +556,33 @@ __global__ void __launch_bounds__(256) attn_cross_bwd_dkv_kernel(CrossArgs a) {
   slab_store(pslab, dk, lane);
   slab_store(dslab, dv, lane);
   __builtin_amdgcn_wave_barrier();
-  bf16_t* drow = a.dkv + ((long)b * S + k0) * (2L * C) + h * D;
+  bf16_t* drow = a.dkv + ((long)b * S + k0) * lddkv + h * D;
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     const int c = lane + i * 64;
     const int r = c >> 3, col = (c & 7) * 8;
     if (!TAIL || k0 + r < S) {
-      *reinterpret_cast<s8v*>(drow + (long)r * (2L * C) + col) = *reinterpret_cast<const s8v*>(pslab + r * PLD + col);
-      *reinterpret_cast<s8v*>(drow + (long)r * (2L * C) + C + col) =
+      *reinterpret_cast<s8v*>(drow + (long)r * lddkv + col) = *reinterpret_cast<const s8v*>(pslab + r * PLD + col);
+      *reinterpret_cast<s8v*>(drow + (long)r * lddkv + C + col) =
           *reinterpret_cast<const s8v*>(dslab + r * PLD + col);
     }
   }
 }
 
-// grid: ceil(T / 64) query blocks; three waves per SIMD asked for, like the tail variants above
-template <bool TAIL, bool MASK>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) attn_cross_bwd_dq_kernel(CrossArgs a) {
+// grid: ceil(T / 64) query blocks.  Three waves per SIMD are asked for: left alone, the tail and the
+// causal instantiations come out a few index registers above the 168 of three waves (174 and
+// 141 + 32 = 173) and run two; asked, every instantiation fits in 162 or fewer without scratch.
+// The plain non-tail one reaches three waves unasked (136 + 32) but is 4 - 5 % faster per forward +
+// backward call with the request (156 + 0): docs/performance.md, "One generic attention kernel family".
+template <bool TAIL, bool MASK, bool CAUSAL>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) attn_bwd_dq_kernel(GenArgs a) {
+  static_assert(!(MASK && CAUSAL), "a masked causal call carries the triangle in its mask");
   __shared__ __attribute__((aligned(16))) short Ks[KB * LDT];
   __shared__ __attribute__((aligned(16))) short Vs[KB * LDT];
   __shared__ __attribute__((aligned(16))) short Ds[4][16 * PLD];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int b = blockIdx.z, h = blockIdx.y, bx = blockIdx.x;
+  const int b = blockIdx.z, h = blockIdx.y;
+  const int bx = block_x<CAUSAL>();
   const int T = a.T, S = a.S, H = a.H, C = H * D;
   const long ldkv = a.ldkv;
   const int q0 = bx * QB + wave * 16;
@@ -910,7 +610,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) a
 #pragma unroll
   for (int t = 0; t < 4; ++t) dq[t] = f4v{0.f, 0.f, 0.f, 0.f};
   short* dslab = Ds[wave];
-  const int nkb = (klen + KB - 1) / KB;  // key blocks entirely past key_len are not read
+  int nkb = (klen + KB - 1) / KB;  // key blocks entirely past key_len are not read
+  // causal: key blocks past the diagonal one (QB == KB) are entirely in the future
+  if constexpr (CAUSAL) nkb = nkb < bx + 1 ? nkb : bx + 1;
   for (int kb = 0; kb < nkb; ++kb) {
     const int k0 = kb * KB;
     MaskRaw mraw;
@@ -921,6 +623,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) a
     uint32_t vis = 0;
     if constexpr (MASK) vis = mask_pack_q(mraw);  // here: the mask bytes arrive before the tile's
     __syncthreads();
+    const bool diag = CAUSAL && kb == bx;  // the only block that needs key <= q
     f4v s[4], dp[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
@@ -938,6 +641,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) a
       for (int r = 0; r < 4; ++r) {
         const uint32_t q = q0 + (lane >> 4) * 4 + r;
         bool seen = key < klen;
+        if constexpr (CAUSAL) seen = seen && (!diag || key <= (int)q);
         if constexpr (MASK) seen = seen && ((vis >> (4 * t + r)) & 1u);
         const float pr = seen ? exp2f(s[t][r] * c2 - ls[r]) : 0.f;
         const float mul = a.drop.on ? drop_mul(a.drop, bhts + (q * (uint32_t)S + (uint32_t)key)) : 1.f;
@@ -965,7 +669,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) a
     const int c = lane + i * 64;
     const int r = c >> 3, col = (c & 7) * 8;
     if (!TAIL || q0 + r < T)
-      *reinterpret_cast<s8v*>(a.dq + ((long)b * T + q0 + r) * C + h * D + col) =
+      *reinterpret_cast<s8v*>(a.dq + ((long)b * T + q0 + r) * a.lddq + h * D + col) =
           *reinterpret_cast<const s8v*>(dslab + r * PLD + col);
   }
 }
@@ -1296,24 +1000,6 @@ __global__ void __launch_bounds__(SQ * 4) attn_fwd_short_kernel(AttnArgs a) {
 
 bool shape_ok(int S, int H) { return S > 0 && H > 0; }
 
-static_assert(QB == KB, "one grid for the key-block and the query-block kernels; causal diagonal block = own block");
-dim3 block_grid(const AttnArgs& a) { return dim3((a.S + QB - 1) / QB, a.H, a.B); }
-
-template <bool CAUSAL>
-void launch_fwd(const AttnArgs& a, hipStream_t s) {
-  if (a.S % QB) attn_fwd_kernel<true, CAUSAL><<<block_grid(a), 256, 0, s>>>(a);
-  else attn_fwd_kernel<false, CAUSAL><<<block_grid(a), 256, 0, s>>>(a);
-}
-template <bool CAUSAL>
-void launch_bwd_dkv(const AttnArgs& a, hipStream_t s) {
-  if (a.S % QB) attn_bwd_dkv_kernel<true, CAUSAL><<<block_grid(a), 256, 0, s>>>(a);
-  else attn_bwd_dkv_kernel<false, CAUSAL><<<block_grid(a), 256, 0, s>>>(a);
-}
-template <bool CAUSAL>
-void launch_bwd_dq(const AttnArgs& a, hipStream_t s) {
-  if (a.S % QB) attn_bwd_dq_kernel<true, CAUSAL><<<block_grid(a), 256, 0, s>>>(a);
-  else attn_bwd_dq_kernel<false, CAUSAL><<<block_grid(a), 256, 0, s>>>(a);
-}
 // S = 64 / 128 only
 template <bool CAUSAL>
 void launch_fwd_short(const AttnArgs& a, hipStream_t s) {
@@ -1329,30 +1015,45 @@ void launch_bwd_fused(const AttnArgs& a, hipStream_t s) {
 bool cross_shape_ok(int B, int T, int S, int H) {
   return B > 0 && T > 0 && S > 0 && H > 0 && (long)T * S <= 0x7fffffffL;  // q*S + key is a 32-bit index
 }
-bool cross_tail(const CrossArgs& a) { return a.T % QB != 0 || a.S % KB != 0; }
-dim3 cross_qgrid(const CrossArgs& a) { return dim3((a.T + QB - 1) / QB, a.H, a.B); }
-dim3 cross_kgrid(const CrossArgs& a) { return dim3((a.S + KB - 1) / KB, a.H, a.B); }
 // mask strides: non-negative, and a (batch, head) slice addressable with 32-bit offsets
 bool cross_mask_ok(const uint8_t* mask, long sb, long sh, long st, int T, int S) {
   return !mask || (sb >= 0 && sh >= 0 && st >= 0 && (long)(T - 1) * st + S <= 0x7fffffffL);
 }
-void cross_set_mask(CrossArgs& a, const uint8_t* mask, long sb, long sh, long st) {
+void cross_set_mask(GenArgs& a, const uint8_t* mask, long sb, long sh, long st) {
   a.mask = mask; a.msb = sb; a.msh = sh; a.mst = st;
 }
-template <bool MASK>
-void launch_cross_fwd(const CrossArgs& a, hipStream_t s) {
-  if (cross_tail(a)) attn_cross_fwd_kernel<true, MASK><<<cross_qgrid(a), 256, 0, s>>>(a);
-  else attn_cross_fwd_kernel<false, MASK><<<cross_qgrid(a), 256, 0, s>>>(a);
+// The generic kernels' view of a packed-qkv call: Q and K | V, and their gradients, are column
+// ranges of rows at pitch 3C
+GenArgs self_args(const AttnArgs& s) {
+  const int C = s.H * D;
+  GenArgs a{};
+  a.q = s.qkv; a.kv = s.qkv + C; a.dout = s.dout; a.ctx = s.ctx; a.dq = s.dqkv;
+  a.dkv = s.dqkv ? s.dqkv + C : nullptr;  // forward: no gradients
+  a.lse = s.lse; a.dvec = s.dvec; a.key_len = s.key_len;
+  a.ldq = a.ldkv = a.lddq = a.lddkv = 3L * C;
+  a.B = s.B; a.T = a.S = s.S; a.H = s.H; a.scale = s.scale; a.drop = s.drop;
+  return a;
 }
-template <bool MASK>
-void launch_cross_bwd_dkv(const CrossArgs& a, hipStream_t s) {
-  if (cross_tail(a)) attn_cross_bwd_dkv_kernel<true, MASK><<<cross_kgrid(a), 256, 0, s>>>(a);
-  else attn_cross_bwd_dkv_kernel<false, MASK><<<cross_kgrid(a), 256, 0, s>>>(a);
+
+// The generic launchers; (MASK, CAUSAL) is (false, false), (true, false) or (false, true)
+static_assert(QB == KB, "causal: one grid for the key-block and the query-block kernels, diagonal block = own block");
+bool gen_tail(const GenArgs& a) { return a.T % QB != 0 || a.S % KB != 0; }
+dim3 gen_qgrid(const GenArgs& a) { return dim3((a.T + QB - 1) / QB, a.H, a.B); }
+dim3 gen_kgrid(const GenArgs& a) { return dim3((a.S + KB - 1) / KB, a.H, a.B); }
+template <bool MASK, bool CAUSAL>
+void launch_fwd(const GenArgs& a, hipStream_t s) {
+  if (gen_tail(a)) attn_fwd_kernel<true, MASK, CAUSAL><<<gen_qgrid(a), 256, 0, s>>>(a);
+  else attn_fwd_kernel<false, MASK, CAUSAL><<<gen_qgrid(a), 256, 0, s>>>(a);
 }
-template <bool MASK>
-void launch_cross_bwd_dq(const CrossArgs& a, hipStream_t s) {
-  if (cross_tail(a)) attn_cross_bwd_dq_kernel<true, MASK><<<cross_qgrid(a), 256, 0, s>>>(a);
-  else attn_cross_bwd_dq_kernel<false, MASK><<<cross_qgrid(a), 256, 0, s>>>(a);
+template <bool MASK, bool CAUSAL>
+void launch_bwd_dkv(const GenArgs& a, hipStream_t s) {
+  if (gen_tail(a)) attn_bwd_dkv_kernel<true, MASK, CAUSAL><<<gen_kgrid(a), 256, 0, s>>>(a);
+  else attn_bwd_dkv_kernel<false, MASK, CAUSAL><<<gen_kgrid(a), 256, 0, s>>>(a);
+}
+template <bool MASK, bool CAUSAL>
+void launch_bwd_dq(const GenArgs& a, hipStream_t s) {
+  if (gen_tail(a)) attn_bwd_dq_kernel<true, MASK, CAUSAL><<<gen_qgrid(a), 256, 0, s>>>(a);
+  else attn_bwd_dq_kernel<false, MASK, CAUSAL><<<gen_qgrid(a), 256, 0, s>>>(a);
 }
 
 // CLOUD_AMD_ATTN_FUSED_BWD=0 keeps the three-kernel backward at S <= 128 (A/B runs)
@@ -1383,8 +1084,8 @@ int ca_attn_fwd(const bf16_t* qkv, bf16_t* ctx, float* lse, const int* key_len, 
     CA_LAUNCH_CHECK();
     return 0;
   }
-  if (causal) launch_fwd<true>(a, s);
-  else launch_fwd<false>(a, s);
+  if (causal) launch_fwd<false, true>(self_args(a), s);
+  else launch_fwd<false, false>(self_args(a), s);
   CA_LAUNCH_CHECK();
   return 0;
 }
@@ -1406,11 +1107,12 @@ int ca_attn_bwd(const bf16_t* qkv, const bf16_t* out, const bf16_t* dout, const 
   const long rows = (long)B * S * H;
   attn_bwd_prep_kernel<<<ca_cdiv(rows, 32), 256, 0, s>>>(a);
   CA_LAUNCH_CHECK();
-  if (causal) launch_bwd_dkv<true>(a, s);
-  else launch_bwd_dkv<false>(a, s);
+  const GenArgs g = self_args(a);
+  if (causal) launch_bwd_dkv<false, true>(g, s);
+  else launch_bwd_dkv<false, false>(g, s);
   CA_LAUNCH_CHECK();
-  if (causal) launch_bwd_dq<true>(a, s);
-  else launch_bwd_dq<false>(a, s);
+  if (causal) launch_bwd_dq<false, true>(g, s);
+  else launch_bwd_dq<false, false>(g, s);
   CA_LAUNCH_CHECK();
   return 0;
 }
@@ -1425,12 +1127,12 @@ int ca_attn_cross_fwd(const bf16_t* q, const bf16_t* kv, bf16_t* ctx, float* lse
                       const uint8_t* mask, long msb, long msh, long mst, int B, int T, int S, int H, long ldq,
                       long ldkv, float scale, float p_drop, uint64_t seed, hipStream_t s) {
   if (!cross_shape_ok(B, T, S, H) || !cross_mask_ok(mask, msb, msh, mst, T, S)) return -1;
-  CrossArgs a{};
+  GenArgs a{};
   a.q = q; a.kv = kv; a.ctx = ctx; a.lse = lse; a.key_len = key_len; a.ldq = ldq; a.ldkv = ldkv;
   a.B = B; a.T = T; a.S = S; a.H = H; a.scale = scale; a.drop = make_drop(p_drop, seed);
   cross_set_mask(a, mask, msb, msh, mst);
-  if (mask) launch_cross_fwd<true>(a, s);
-  else launch_cross_fwd<false>(a, s);
+  if (mask) launch_fwd<true, false>(a, s);
+  else launch_fwd<false, false>(a, s);
   CA_LAUNCH_CHECK();
   return 0;
 }
@@ -1445,16 +1147,16 @@ int ca_attn_cross_bwd(const bf16_t* q, const bf16_t* kv, const bf16_t* out, cons
   p.out = out; p.dout = dout; p.dvec = dvec; p.B = B; p.S = T; p.H = H;
   attn_bwd_prep_kernel<<<ca_cdiv((long)B * T * H, 32), 256, 0, s>>>(p);
   CA_LAUNCH_CHECK();
-  CrossArgs a{};
+  GenArgs a{};
   a.q = q; a.kv = kv; a.dout = dout; a.lse = const_cast<float*>(lse); a.dvec = dvec; a.dq = dq; a.dkv = dkv;
-  a.key_len = key_len; a.ldq = ldq; a.ldkv = ldkv;
+  a.key_len = key_len; a.ldq = ldq; a.ldkv = ldkv; a.lddq = (long)H * D; a.lddkv = 2L * H * D;
   a.B = B; a.T = T; a.S = S; a.H = H; a.scale = scale; a.drop = make_drop(p_drop, seed);
   cross_set_mask(a, mask, msb, msh, mst);
-  if (mask) launch_cross_bwd_dkv<true>(a, s);
-  else launch_cross_bwd_dkv<false>(a, s);
+  if (mask) launch_bwd_dkv<true, false>(a, s);
+  else launch_bwd_dkv<false, false>(a, s);
   CA_LAUNCH_CHECK();
-  if (mask) launch_cross_bwd_dq<true>(a, s);
-  else launch_cross_bwd_dq<false>(a, s);
+  if (mask) launch_bwd_dq<true, false>(a, s);
+  else launch_bwd_dq<false, false>(a, s);
   CA_LAUNCH_CHECK();
   return 0;
 }

@@ -171,9 +171,11 @@ def test_cross_attention_vs_fp64(T, S, key_len, p):
 
 @pytest.mark.parametrize("S", [100, 192, 200])
 def test_cross_equals_self_attention_bitwise(S):
-    """T == S, q and kv the column views of one packed qkv (both at pitch 3C): the stores of the
-    non-causal generic self-attention kernels, bit for bit.  (64 and 128 dispatch to the
-    one-workgroup kernels, which sum in another order, and are not compared.)"""
+    """T == S, q and kv the column views of one packed qkv (both at pitch 3C): the self- and the
+    cross-attention entry points reach the same generic kernels, one with its gradients at pitch 3C
+    inside dqkv, the other with contiguous dq and dkv, and both store the same bits.  (Self-attention
+    at 64 and 128 dispatches to the one-workgroup kernels, which sum in another order, and is not
+    compared.)"""
     from cloud_amd.ops import raw
 
     B, p, seed = 3, 0.1, 4321
