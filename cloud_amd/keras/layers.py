@@ -378,8 +378,9 @@ class MultiHeadAttention(Layer):
 
     Self-attention (``query is value``, no ``key`` or the same tensor) without an
     ``attention_mask`` and without ``return_attention_scores`` is one packed projection,
-    ``ops.attention`` and the output projection: under the mixed policy with ``key_dim == 64``
-    all three run on the in-tree kernels, forward and backward.  Cross-attention (``query`` is
+    ``ops.attention`` and the output projection: under the mixed policy with ``key_dim`` in
+    ``ops.raw.ATTN_HEAD_DIMS`` (32, 64 or 128) all three run on the in-tree kernels, forward and
+    backward.  Cross-attention (``query`` is
     not ``value``) without a mask, returned scores or the causal flag is native under the same
     conditions: the Q projection from the first third of ``qkv_kernel``, the K | V projection
     from the other two as one GEMM (two and a concatenation when ``key`` is a tensor of its own),
@@ -492,7 +493,7 @@ class MultiHeadAttention(Layer):
             q, kv = cross_proj()
             ctx = ops.cross_attention(q, kv, H, None, p, bool(training))
             return dense_op(ctx, self.out_kernel, self.out_bias, None)
-        if (not return_attention_scores and dt == torch.bfloat16 and D == 64
+        if (not return_attention_scores and dt == torch.bfloat16 and D in ops.raw.ATTN_HEAD_DIMS
                 and ops.use_native(query, value, key)):
             # masked attention (an attention_mask, or causal cross-attention) on the mask kernels
             allowed = None

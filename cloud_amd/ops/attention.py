@@ -7,8 +7,9 @@ cross-attention of a query projection against a packed K | V projection.
 projection produces and the kernels of ``csrc/kernels/attn.hip`` read in place.  The
 result is ``[B, S, H*D]``.
 
-On MI355X (contiguous bf16 CUDA tensors, ``D == 64``) forward and backward run on the
-gfx950 MFMA kernels at any sequence length (S = 64 / 128 on the one-workgroup kernels);
+On MI355X (contiguous bf16 CUDA tensors, ``D`` in ``raw.ATTN_HEAD_DIMS`` = 32, 64, 128) forward
+and backward run on the gfx950 MFMA kernels at any sequence length (D = 64 at S = 64 / 128 on the
+one-workgroup kernels);
 with ``causal=True`` they skip the 64x64 score blocks that lie entirely in the future.  The
 backward recomputes the probabilities from the saved log-sum-exp and regenerates the
 dropout mask from the saved seed.  CPU tensors, other dtypes and other head dimensions run
@@ -42,7 +43,8 @@ class _AttentionFn(torch.autograd.Function):
     def forward(ctx, qkv, key_len, H, scale, p, seed, causal):
         B, S, _ = qkv.shape
         q2 = qkv.view(B * S, -1)
-        out, lse = raw.attn_fwd(q2, B, S, H, key_len, p, seed, scale=scale, causal=causal)
+        out, lse = raw.attn_fwd(q2, B, S, H, key_len, p, seed, scale=scale, causal=causal,
+                                head_dim=q2.shape[1] // (3 * H))
         ctx.save_for_backward(q2, out, lse, key_len)
         ctx.cfg = (B, S, H, scale, p, seed, causal)
         return out.view(B, S, -1)
@@ -52,7 +54,8 @@ class _AttentionFn(torch.autograd.Function):
         q2, out, lse, key_len = ctx.saved_tensors
         B, S, H, scale, p, seed, causal = ctx.cfg
         dout = dout.contiguous().view(B * S, -1)
-        dqkv = raw.attn_bwd(q2, out, dout, lse, B, S, H, key_len, p, seed, scale=scale, causal=causal)
+        dqkv = raw.attn_bwd(q2, out, dout, lse, B, S, H, key_len, p, seed, scale=scale, causal=causal,
+                            head_dim=q2.shape[1] // (3 * H))
         return dqkv.view(B, S, -1), None, None, None, None, None, None
 
 
@@ -65,7 +68,8 @@ class _MaskedAttentionFn(torch.autograd.Function):
         B, S, C3 = qkv.shape
         q2 = qkv.view(B * S, C3)
         C = C3 // 3
-        out, lse = raw.attn_cross_fwd(q2[:, :C], q2[:, C:], B, S, S, H, key_len, p, seed, scale=scale, mask=mask)
+        out, lse = raw.attn_cross_fwd(q2[:, :C], q2[:, C:], B, S, S, H, key_len, p, seed, scale=scale, mask=mask,
+                                      head_dim=C // H)
         ctx.save_for_backward(q2, out, lse, key_len, mask)
         ctx.cfg = (B, S, H, scale, p, seed)
         return out.view(B, S, -1)
@@ -77,7 +81,7 @@ class _MaskedAttentionFn(torch.autograd.Function):
         C = q2.shape[1] // 3
         dout = dout.contiguous().view(B * S, -1)
         dq, dkv = raw.attn_cross_bwd(q2[:, :C], q2[:, C:], out, dout, lse, B, S, S, H, key_len, p, seed, scale=scale,
-                                     mask=mask)
+                                     mask=mask, head_dim=C // H)
         return torch.cat([dq, dkv], dim=1).view(B, S, -1), None, None, None, None, None, None
 
 
@@ -161,7 +165,8 @@ def attention(qkv, num_heads, key_len=None, dropout_p=0.0, training=True, scale=
     mask a query row can lose every key: such a row has a zero context row and sends zero
     gradients.  Natively a masked call runs on the cross-attention kernels, which read the views
     ``qkv[..., :C]`` and ``qkv[..., C:]`` in place and the mask through broadcast strides (no
-    expansion); at S = 64 / 128 it therefore does not take the one-workgroup kernels.
+    expansion); at S = 64 / 128 it therefore does not take the one-workgroup kernels (which are
+    for D = 64 only; the other head dimensions run the generic kernels at every S).
     ``causal=True`` together with a mask ANDs a lower-triangular ``[S, S]`` into the mask in
     PyTorch: that materialises a byte mask of up to ``[B, H, S, S]`` per call and gives up the
     block skipping of the causal kernels (every 64x64 block is computed).  ``mask=None`` runs
@@ -175,7 +180,7 @@ def attention(qkv, num_heads, key_len=None, dropout_p=0.0, training=True, scale=
     if mask is not None:
         B, S = qkv.shape[0], qkv.shape[1]
         m4 = _mask4(mask, B, num_heads, S, S, qkv.device, "attention")
-        if (qkv.dtype == torch.bfloat16 and D == 64 and B > 0 and S > 0 and qkv.is_contiguous()
+        if (qkv.dtype == torch.bfloat16 and D in raw.ATTN_HEAD_DIMS and B > 0 and S > 0 and qkv.is_contiguous()
                 and _ext.use_native(qkv)):
             if causal:
                 m4 = m4 & torch.ones(S, S, dtype=torch.bool, device=qkv.device).tril()
@@ -184,8 +189,8 @@ def attention(qkv, num_heads, key_len=None, dropout_p=0.0, training=True, scale=
                 seed = next_seed()
             return _MaskedAttentionFn.apply(qkv, kl, m4, num_heads, scale, p, int(seed) if p > 0 else 0)
         return _reference(qkv, num_heads, key_len, scale, p, bool(causal), m4)
-    if (qkv.dtype == torch.bfloat16 and D == 64 and qkv.shape[0] > 0 and qkv.shape[1] > 0 and qkv.is_contiguous()
-            and _ext.use_native(qkv)):
+    if (qkv.dtype == torch.bfloat16 and D in raw.ATTN_HEAD_DIMS and qkv.shape[0] > 0 and qkv.shape[1] > 0
+            and qkv.is_contiguous() and _ext.use_native(qkv)):
         kl = None if key_len is None else key_len.to(device=qkv.device, dtype=torch.int32).contiguous()
         if p > 0 and seed is None:
             seed = next_seed()
@@ -199,7 +204,8 @@ class _CrossAttentionFn(torch.autograd.Function):
         B, T, _ = q.shape
         S = kv.shape[1]
         q2, kv2 = q.view(B * T, -1), kv.view(B * S, -1)
-        out, lse = raw.attn_cross_fwd(q2, kv2, B, T, S, H, key_len, p, seed, scale=scale, mask=mask)
+        out, lse = raw.attn_cross_fwd(q2, kv2, B, T, S, H, key_len, p, seed, scale=scale, mask=mask,
+                                      head_dim=q2.shape[1] // H)
         ctx.save_for_backward(q2, kv2, out, lse, key_len, mask)
         ctx.cfg = (B, T, S, H, scale, p, seed)
         return out.view(B, T, -1)
@@ -209,7 +215,8 @@ class _CrossAttentionFn(torch.autograd.Function):
         q2, kv2, out, lse, key_len, mask = ctx.saved_tensors
         B, T, S, H, scale, p, seed = ctx.cfg
         dout = dout.contiguous().view(B * T, -1)
-        dq, dkv = raw.attn_cross_bwd(q2, kv2, out, dout, lse, B, T, S, H, key_len, p, seed, scale=scale, mask=mask)
+        dq, dkv = raw.attn_cross_bwd(q2, kv2, out, dout, lse, B, T, S, H, key_len, p, seed, scale=scale, mask=mask,
+                                     head_dim=q2.shape[1] // H)
         return dq.view(B, T, -1), dkv.view(B, S, -1), None, None, None, None, None, None
 
 
@@ -263,7 +270,8 @@ def cross_attention(q, kv, num_heads, key_len=None, dropout_p=0.0, training=True
     gradients to ``q`` and ``kv`` (a softmax over nothing is defined as all zeros, on both paths);
     a key no query sees gets zero gradients.
 
-    bf16 CUDA tensors with ``D == 64`` run on the gfx950 kernels, forward and backward
+    bf16 CUDA tensors with ``D`` in ``raw.ATTN_HEAD_DIMS`` (32, 64, 128) run on the gfx950 kernels,
+    forward and backward
     (non-contiguous inputs are made contiguous first); everything else (CPU, other dtypes,
     other head dimensions) runs the same math in fp32 PyTorch (fp64 for fp64 inputs).  The two
     paths draw different dropout masks: the HIP kernels hash ``(seed, element index)`` with
@@ -286,7 +294,8 @@ def cross_attention(q, kv, num_heads, key_len=None, dropout_p=0.0, training=True
     scale = 1.0 / math.sqrt(D) if scale is None else float(scale)
     p = float(dropout_p) if training else 0.0
     m4 = None if mask is None else _mask4(mask, q.shape[0], H, q.shape[1], kv.shape[1], q.device, "cross_attention")
-    if q.dtype == torch.bfloat16 and D == 64 and q.numel() > 0 and kv.numel() > 0 and _ext.use_native(q, kv):
+    if (q.dtype == torch.bfloat16 and D in raw.ATTN_HEAD_DIMS and q.numel() > 0 and kv.numel() > 0
+            and _ext.use_native(q, kv)):
         kl = None if key_len is None else key_len.to(device=q.device, dtype=torch.int32).contiguous()
         if p > 0 and seed is None:
             seed = next_seed()

@@ -961,35 +961,50 @@ def embed_bwd(dh, ids, tts, dword, dpos, dtype_, seq_len, n_types, pos_offset=0,
                                "(CLOUD_AMD_DETERMINISTIC=1)" % (C, n_types))
 
 
-def attn_fwd(qkv, B, S, H, key_len=None, p_drop=0.0, seed=0, scale=None, causal=False):
-    """qkv [B*S, 3*H*64] -> (ctx [B*S, H*64], lse [B, H, S]).  Any S; S = 64 / 128 take the
-    one-workgroup kernels.  ``causal``: key j is visible to query i iff j <= i (and j < key_len)."""
+# Head dimensions the attention kernels are instantiated for (csrc/kernels/attn.hip); the ops and
+# the Keras layer route exactly these to the kernels.
+ATTN_HEAD_DIMS = (32, 64, 128)
+
+
+def _attn_head_dim(head_dim):
+    if head_dim not in ATTN_HEAD_DIMS:
+        raise ValueError(f"attention kernels exist for head_dim in {ATTN_HEAD_DIMS}, got {head_dim}")
+    return int(head_dim)
+
+
+def attn_fwd(qkv, B, S, H, key_len=None, p_drop=0.0, seed=0, scale=None, causal=False, *, head_dim=64):
+    """qkv [B*S, 3*H*D] -> (ctx [B*S, H*D], lse [B, H, S]) for ``D = head_dim`` in ``ATTN_HEAD_DIMS``.
+    Any S; D = 64 at S = 64 / 128 takes the one-workgroup kernels.  ``scale`` defaults to
+    ``1 / sqrt(D)``.  ``causal``: key j is visible to query i iff j <= i (and j < key_len)."""
+    D = _attn_head_dim(head_dim)
     ext = _ext.load(required=True)
-    C = H * 64
+    C = H * D
     ctx = torch.empty((B * S, C), dtype=torch.bfloat16, device=qkv.device)
     lse = torch.empty((B, H, S), dtype=torch.float32, device=qkv.device)
-    scale = 1.0 / 8.0 if scale is None else scale
-    ext.attn_fwd(qkv.data_ptr(), ctx.data_ptr(), lse.data_ptr(), _ext.ptr(key_len), B, S, H, float(scale),
+    scale = D ** -0.5 if scale is None else scale
+    ext.attn_fwd(qkv.data_ptr(), ctx.data_ptr(), lse.data_ptr(), _ext.ptr(key_len), B, S, H, D, float(scale),
                  float(p_drop), int(seed), bool(causal), _st(qkv.device))
     return ctx, lse
 
 
-def attn_bwd(qkv, ctx, dctx, lse, B, S, H, key_len=None, p_drop=0.0, seed=0, scale=None, causal=False):
+def attn_bwd(qkv, ctx, dctx, lse, B, S, H, key_len=None, p_drop=0.0, seed=0, scale=None, causal=False, *,
+             head_dim=64):
+    D = _attn_head_dim(head_dim)
     ext = _ext.load(required=True)
     dqkv = torch.empty_like(qkv)
     dvec = torch.empty_like(lse)
-    scale = 1.0 / 8.0 if scale is None else scale
+    scale = D ** -0.5 if scale is None else scale
     ext.attn_bwd(qkv.data_ptr(), ctx.data_ptr(), dctx.data_ptr(), lse.data_ptr(), dvec.data_ptr(), dqkv.data_ptr(),
-                 _ext.ptr(key_len), B, S, H, float(scale), float(p_drop), int(seed), bool(causal),
+                 _ext.ptr(key_len), B, S, H, D, float(scale), float(p_drop), int(seed), bool(causal),
                  _st(qkv.device))
     return dqkv
 
 
-def _cross_operands(q, kv, B, T, S, H, mask=None):
+def _cross_operands(q, kv, B, T, S, H, mask=None, D=64):
     """The shape, pitch and alignment contract of the cross-attention kernels (16-byte loads), and
     of their byte mask.  Returns the mask's ``(pointer, batch, head, row)`` element strides with 0
-    for its size-1 (broadcast) axes; ``(0, 0, 0, 0)`` without a mask."""
-    C = H * 64
+    for its size-1 (broadcast) axes; ``(0, 0, 0, 0)`` without a mask.  ``D``: the head dimension."""
+    C = H * D
     for name, t, shape in (("q", q, (B * T, C)), ("kv", kv, (B * S, 2 * C))):
         if t.dtype != torch.bfloat16 or tuple(t.shape) != shape:
             raise ValueError(f"attn_cross: {name} must be bf16 {shape}, got {t.dtype} {tuple(t.shape)}")
@@ -1018,8 +1033,9 @@ def _cross_operands(q, kv, B, T, S, H, mask=None):
     return mask.data_ptr(), sb, sh, st
 
 
-def attn_cross_fwd(q, kv, B, T, S, H, key_len=None, p_drop=0.0, seed=0, scale=None, *, mask=None):
-    """Cross-attention: q [B*T, H*64] and kv [B*S, 2*H*64] (K | V) -> (ctx [B*T, H*64], lse [B, H, T]).
+def attn_cross_fwd(q, kv, B, T, S, H, key_len=None, p_drop=0.0, seed=0, scale=None, *, mask=None, head_dim=64):
+    """Cross-attention: q [B*T, H*D] and kv [B*S, 2*H*D] (K | V) -> (ctx [B*T, H*D], lse [B, H, T]) for
+    ``D = head_dim`` in ``ATTN_HEAD_DIMS``; ``scale`` defaults to ``1 / sqrt(D)``.
     Any T and S; both operands may be column slices of wider tensors (unit column stride, the
     row pitch is ``stride(0)``).  ``key_len`` [B] int32: the number of valid leading keys, clamped
     to [1, S].  The dropout element index is ``(b*H + h)*T*S + q*S + key``.
@@ -1028,34 +1044,37 @@ def attn_cross_fwd(q, kv, B, T, S, H, key_len=None, p_drop=0.0, seed=0, scale=No
     stride, any other strides (size-1 axes are broadcast, nothing is materialised).  Query ``q``
     sees ``key`` iff ``key < key_len[b]`` and its mask byte is non-zero.  A query that sees no key
     gets a zero context row and ``lse = 0``."""
+    D = _attn_head_dim(head_dim)
     ext = _ext.load(required=True)
-    mptr, msb, msh, mst = _cross_operands(q, kv, B, T, S, H, mask)
-    ctx = torch.empty((B * T, H * 64), dtype=torch.bfloat16, device=q.device)
+    mptr, msb, msh, mst = _cross_operands(q, kv, B, T, S, H, mask, D)
+    ctx = torch.empty((B * T, H * D), dtype=torch.bfloat16, device=q.device)
     lse = torch.empty((B, H, T), dtype=torch.float32, device=q.device)
-    scale = 1.0 / 8.0 if scale is None else scale
+    scale = D ** -0.5 if scale is None else scale
     ext.attn_cross_fwd(q.data_ptr(), kv.data_ptr(), ctx.data_ptr(), lse.data_ptr(), _ext.ptr(key_len), mptr, msb, msh,
-                       mst, B, T, S, H, q.stride(0), kv.stride(0), float(scale), float(p_drop), int(seed),
+                       mst, B, T, S, H, D, q.stride(0), kv.stride(0), float(scale), float(p_drop), int(seed),
                        _st(q.device))
     return ctx, lse
 
 
-def attn_cross_bwd(q, kv, ctx, dctx, lse, B, T, S, H, key_len=None, p_drop=0.0, seed=0, scale=None, *, mask=None):
-    """-> (dq [B*T, H*64], dkv [B*S, 2*H*64]), both contiguous; ``ctx`` and ``dctx`` are contiguous
-    [B*T, H*64].  dK / dV rows of keys >= key_len are zeros.  ``mask`` as in ``attn_cross_fwd`` (the
+def attn_cross_bwd(q, kv, ctx, dctx, lse, B, T, S, H, key_len=None, p_drop=0.0, seed=0, scale=None, *, mask=None,
+                   head_dim=64):
+    """-> (dq [B*T, H*D], dkv [B*S, 2*H*D]), both contiguous; ``ctx`` and ``dctx`` are contiguous
+    [B*T, H*D].  dK / dV rows of keys >= key_len are zeros.  ``mask`` as in ``attn_cross_fwd`` (the
     same one): dQ rows of queries that see no key and dK / dV rows of keys no query sees are zeros."""
+    D = _attn_head_dim(head_dim)
     ext = _ext.load(required=True)
-    mptr, msb, msh, mst = _cross_operands(q, kv, B, T, S, H, mask)
-    C = H * 64
+    mptr, msb, msh, mst = _cross_operands(q, kv, B, T, S, H, mask, D)
+    C = H * D
     for name, t in (("ctx", ctx), ("dctx", dctx)):
         if t.dtype != torch.bfloat16 or tuple(t.shape) != (B * T, C) or not t.is_contiguous():
             raise ValueError(f"attn_cross_bwd: {name} must be contiguous bf16 {(B * T, C)}")
     dq = torch.empty((B * T, C), dtype=torch.bfloat16, device=q.device)
     dkv = torch.empty((B * S, 2 * C), dtype=torch.bfloat16, device=q.device)
     dvec = torch.empty_like(lse)
-    scale = 1.0 / 8.0 if scale is None else scale
+    scale = D ** -0.5 if scale is None else scale
     ext.attn_cross_bwd(q.data_ptr(), kv.data_ptr(), ctx.data_ptr(), dctx.data_ptr(), lse.data_ptr(), dvec.data_ptr(),
-                       dq.data_ptr(), dkv.data_ptr(), _ext.ptr(key_len), mptr, msb, msh, mst, B, T, S, H, q.stride(0),
-                       kv.stride(0), float(scale), float(p_drop), int(seed), _st(q.device))
+                       dq.data_ptr(), dkv.data_ptr(), _ext.ptr(key_len), mptr, msb, msh, mst, B, T, S, H, D,
+                       q.stride(0), kv.stride(0), float(scale), float(p_drop), int(seed), _st(q.device))
     return dq, dkv
 
 

@@ -127,13 +127,14 @@ int ca_embed_bwd(const bf16_t*, const int32_t*, const int32_t*, float*, float*, 
                  int, float*, unsigned*, hipStream_t);
 int ca_dropout(const bf16_t*, bf16_t*, long, float, uint64_t, hipStream_t);
 int ca_dropout_mask(uint8_t*, long, long, float, uint64_t, hipStream_t);
-int ca_attn_fwd(const bf16_t*, bf16_t*, float*, const int*, int, int, int, float, float, uint64_t, int, hipStream_t);
+int ca_attn_fwd(const bf16_t*, bf16_t*, float*, const int*, int, int, int, int, float, float, uint64_t, int,
+                hipStream_t);
 int ca_attn_bwd(const bf16_t*, const bf16_t*, const bf16_t*, const float*, float*, bf16_t*, const int*, int, int, int,
-                float, float, uint64_t, int, hipStream_t);
+                int, float, float, uint64_t, int, hipStream_t);
 int ca_attn_cross_fwd(const bf16_t*, const bf16_t*, bf16_t*, float*, const int*, const uint8_t*, long, long, long, int,
-                      int, int, int, long, long, float, float, uint64_t, hipStream_t);
+                      int, int, int, int, long, long, float, float, uint64_t, hipStream_t);
 int ca_attn_cross_bwd(const bf16_t*, const bf16_t*, const bf16_t*, const bf16_t*, const float*, float*, bf16_t*,
-                      bf16_t*, const int*, const uint8_t*, long, long, long, int, int, int, int, long, long, float,
+                      bf16_t*, const int*, const uint8_t*, long, long, long, int, int, int, int, int, long, long, float,
                       float, uint64_t, hipStream_t);
 }
 
@@ -525,31 +526,32 @@ PYBIND11_MODULE(_C, m) {
   m.def("dropout_mask", [](u64 m_, long n, long base, float p, u64 seed, u64 s) {
     check(ca_dropout_mask(P(uint8_t*, m_), n, base, p, seed, S(s)), "dropout_mask");
   });
-  m.def("attn_fwd", [](u64 qkv, u64 ctx, u64 lse, u64 klen, int B, int S_, int H, float scale, float p, u64 seed,
-                       bool causal, u64 s) {
-    check(ca_attn_fwd(P(const bf16_t*, qkv), P(bf16_t*, ctx), P(float*, lse), P(const int*, klen), B, S_, H, scale, p,
-                      seed, causal ? 1 : 0, S(s)), "attn_fwd");
+  m.def("attn_fwd", [](u64 qkv, u64 ctx, u64 lse, u64 klen, int B, int S_, int H, int D, float scale, float p,
+                       u64 seed, bool causal, u64 s) {
+    check(ca_attn_fwd(P(const bf16_t*, qkv), P(bf16_t*, ctx), P(float*, lse), P(const int*, klen), B, S_, H, D, scale,
+                      p, seed, causal ? 1 : 0, S(s)), "attn_fwd");
   });
   m.def("attn_bwd", [](u64 qkv, u64 out, u64 dout, u64 lse, u64 dvec, u64 dqkv, u64 klen, int B, int S_, int H,
-                       float scale, float p, u64 seed, bool causal, u64 s) {
+                       int D, float scale, float p, u64 seed, bool causal, u64 s) {
     check(ca_attn_bwd(P(const bf16_t*, qkv), P(const bf16_t*, out), P(const bf16_t*, dout), P(const float*, lse),
-                      P(float*, dvec), P(bf16_t*, dqkv), P(const int*, klen), B, S_, H, scale, p, seed,
+                      P(float*, dvec), P(bf16_t*, dqkv), P(const int*, klen), B, S_, H, D, scale, p, seed,
                       causal ? 1 : 0, S(s)),
           "attn_bwd");
   });
   m.def("attn_cross_fwd", [](u64 q, u64 kv, u64 ctx, u64 lse, u64 klen, u64 mask, long msb, long msh, long mst, int B,
-                             int T, int S_, int H, long ldq, long ldkv, float scale, float p, u64 seed, u64 s) {
+                             int T, int S_, int H, int D, long ldq, long ldkv, float scale, float p, u64 seed,
+                             u64 s) {
     check(ca_attn_cross_fwd(P(const bf16_t*, q), P(const bf16_t*, kv), P(bf16_t*, ctx), P(float*, lse),
-                            P(const int*, klen), P(const uint8_t*, mask), msb, msh, mst, B, T, S_, H, ldq, ldkv,
+                            P(const int*, klen), P(const uint8_t*, mask), msb, msh, mst, B, T, S_, H, D, ldq, ldkv,
                             scale, p, seed, S(s)),
           "attn_cross_fwd");
   });
   m.def("attn_cross_bwd", [](u64 q, u64 kv, u64 out, u64 dout, u64 lse, u64 dvec, u64 dq, u64 dkv, u64 klen, u64 mask,
-                             long msb, long msh, long mst, int B, int T, int S_, int H, long ldq, long ldkv,
+                             long msb, long msh, long mst, int B, int T, int S_, int H, int D, long ldq, long ldkv,
                              float scale, float p, u64 seed, u64 s) {
     check(ca_attn_cross_bwd(P(const bf16_t*, q), P(const bf16_t*, kv), P(const bf16_t*, out), P(const bf16_t*, dout),
                             P(const float*, lse), P(float*, dvec), P(bf16_t*, dq), P(bf16_t*, dkv),
-                            P(const int*, klen), P(const uint8_t*, mask), msb, msh, mst, B, T, S_, H, ldq, ldkv,
+                            P(const int*, klen), P(const uint8_t*, mask), msb, msh, mst, B, T, S_, H, D, ldq, ldkv,
                             scale, p, seed, S(s)),
           "attn_cross_bwd");
   });

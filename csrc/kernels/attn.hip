@@ -1,8 +1,8 @@
-// Fused multi-head attention (K13 in SURVEY.md 2.7) for head_dim 64 on MFMA.
+// Fused multi-head attention (K13 in SURVEY.md 2.7) for head_dim D = 32, 64 or 128 on MFMA.
 //
-// Layout: the QKV projection output qkv[B*S][3*H*64] (Q | K | V, head h at
-// columns h*64 inside each third) is consumed in place -- no head split /
-// transpose copies; the context is written to ctx[B*S][H*64].
+// Layout: the QKV projection output qkv[B*S][3*H*D] (Q | K | V, head h at
+// columns h*D inside each third) is consumed in place -- no head split /
+// transpose copies; the context is written to ctx[B*S][H*D].
 //
 // Forward (one workgroup = 64 queries of one (batch, head), 4 waves x 16 rows):
 //   S = Q K^T * scale over 64-key blocks, online softmax in registers (exp2
@@ -23,8 +23,17 @@
 // that serves self-attention on the packed qkv and cross-attention on separate q and kv, two
 // one-workgroup kernels for self-attention at S = 64 / 128 (below), and the prep kernel.
 //
-// Shapes: any S; self-attention at S = 64 / 128 takes the one-workgroup kernels, every other
-// call the generic ones on ceil(S / 64) blocks.  S % 64 != 0 runs their TAIL instantiation, which
+// Head dim: a compile-time parameter HD of the generic family and of the prep kernel.  Query and
+// key blocks are 64 x 64 at every HD, so masks, causal skipping, block_x, the tail rules and the
+// dropout element index do not depend on it.  What scales: the contractions over the head dim
+// (Q K^T, V dO^T) take HD / 32 MFMA steps in ascending order, the outputs (P V, dV, dK, dQ) have
+// HD / 16 tiles, the 64-row LDS tiles are 64 x HD at pitch HD + 8, and the outputs are staged
+// through the per-wave 16 x 72 slabs in 64-column halves at HD = 128.  The HD = 64 instantiations
+// are, instruction for instruction, the code from before the parameter existed; the one-workgroup
+// kernels are HD = 64 only.
+//
+// Shapes: any S; self-attention with D = 64 at S = 64 / 128 takes the one-workgroup kernels, every
+// other call the generic ones on ceil(S / 64) blocks.  S % 64 != 0 runs their TAIL instantiation, which
 // only masks: fragment rows >= S are clamped to row S - 1, tile rows >= S are zero-filled in LDS,
 // lse / Dv of queries >= S are not read (dKV: p = dS = 0 for those columns), and only rows
 // < S are stored.
@@ -50,7 +59,7 @@
 namespace {
 using namespace ca;
 
-constexpr int D = 64;     // head dim
+constexpr int D = 64;     // head dim of the one-workgroup kernels (the generic ones: template HD)
 constexpr int QB = 64;    // queries per workgroup
 constexpr int KB = 64;    // keys per block
 constexpr int LDT = 72;   // LDS row pitch (64 + 8 pad) of every 64x64 tile
@@ -59,22 +68,23 @@ constexpr float LOG2E = 1.4426950408889634f;
 
 // TAIL (S % 64 != 0): only the first `nrows` (>= 1) rows exist; the others are zero-filled in
 // LDS, not read -- they are MFMA operands, and 0 x (whatever lies behind the tensor) may be NaN.
-template <bool TAIL>
+template <bool TAIL, int HD>
 __device__ __forceinline__ void tile_load(short* lds, const bf16_t* g, long ld, int tid, int nrows) {
-  // 64 rows x 64 bf16 (8 chunks of 16 B per row): 512 chunks, 2 per thread
+  // 64 rows x HD bf16 (HD / 8 chunks of 16 B per row) at pitch HD + 8: 8 HD chunks, HD / 32 per thread
+  constexpr int CPR = HD / 8, CSH = HD == 32 ? 2 : (HD == 64 ? 3 : 4), LDH = HD + 8;
 #pragma unroll
-  for (int i = 0; i < 2; ++i) {
+  for (int i = 0; i < HD / 32; ++i) {
     const int c = tid + i * 256;
-    const int r = c >> 3, col = (c & 7) * 8;
+    const int r = c >> CSH, col = (c & (CPR - 1)) * 8;
     if constexpr (TAIL) {
       // branch-free (the tile's loads stay in flight together): a row past the end loads the
       // last existing row (nrows >= 1) and is then replaced by zeros
       const int rr = r < nrows ? r : nrows - 1;
       s8v v = *reinterpret_cast<const s8v*>(g + (long)rr * ld + col);
       if (r >= nrows) v = s8v{0, 0, 0, 0, 0, 0, 0, 0};
-      *reinterpret_cast<s8v*>(lds + r * LDT + col) = v;
+      *reinterpret_cast<s8v*>(lds + r * LDH + col) = v;
     } else {
-      *reinterpret_cast<s8v*>(lds + r * LDT + col) = *reinterpret_cast<const s8v*>(g + (long)r * ld + col);
+      *reinterpret_cast<s8v*>(lds + r * LDH + col) = *reinterpret_cast<const s8v*>(g + (long)r * ld + col);
     }
   }
 }
@@ -87,10 +97,11 @@ __device__ __forceinline__ int frag_row(int row, int S) {
   return row;
 }
 
-// C-layout 16x64 fp32 (4 tiles) -> bf16 slab [16][PLD] of this wave
-__device__ __forceinline__ void slab_store(short* slab, const f4v (&v)[4], int lane) {
+// C-layout 16 x 16 NT fp32 (NT <= 4 tiles) -> bf16 slab [16][PLD] of this wave
+template <int NT>
+__device__ __forceinline__ void slab_store(short* slab, const f4v (&v)[NT], int lane) {
 #pragma unroll
-  for (int t = 0; t < 4; ++t)
+  for (int t = 0; t < NT; ++t)
 #pragma unroll
     for (int r = 0; r < 4; ++r) slab[((lane >> 4) * 4 + r) * PLD + t * 16 + (lane & 15)] = (short)f2bf(v[t][r]);
 }
@@ -104,6 +115,95 @@ __device__ __forceinline__ bf16x8 slab_frag(const short* slab, int kk, int lane)
 // A fragment straight from global rows (row-major, k contiguous)
 __device__ __forceinline__ bf16x8 gfrag(const bf16_t* rowp, int kk, int lane) {
   return __builtin_bit_cast(bf16x8, *reinterpret_cast<const s8v*>(rowp + kk * 32 + 8 * (lane >> 4)));
+}
+
+// MFMA operand fragments of an LDS tile at row pitch LD (the lane mapping of read_frag in
+// ca_mfma_core.h, which is tied to pitch 72): k contiguous ...
+template <int LD>
+__device__ __forceinline__ bf16x8 frag_kc(const short* lds, int r0, int k0, int lane) {
+  s8v v = *reinterpret_cast<const s8v*>(lds + (r0 + (lane & 15)) * LD + k0 + 8 * (lane >> 4));
+  return __builtin_bit_cast(bf16x8, v);
+}
+// ... and element (r, k) at lds[k * LD + r] (r contiguous): the transposed read
+template <int LD>
+__device__ __forceinline__ bf16x8 frag_nc(const short* lds, int r0, int k0, int lane) {
+  const int g = lane >> 4, q = (lane & 15) >> 2, p = lane & 3;
+  const short* b0 = lds + (k0 + 8 * g + q) * LD + r0 + 4 * p;
+  s4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4v*)(b0));
+  s4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4v*)(b0 + 4 * LD));
+  s8v v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+  return __builtin_bit_cast(bf16x8, v);
+}
+
+// Output staging of the generic kernels: C-layout 16 x HD fp32 (HD / 16 tiles) -> 16-B row stores,
+// through the wave's [16][PLD] slab in column groups of SW = min(HD, 64): one group at HD <= 64,
+// two 64-column halves at HD = 128 (wave barriers order a half's row reads before the next half's
+// writes).  row_ok(r): row r of the wave's 16 exists.
+template <int HD>
+struct Stage {
+  static constexpr int SW = HD < 64 ? HD : 64;  // columns per group
+  static constexpr int NG = HD / SW;            // groups
+  static constexpr int NT = SW / 16;            // C tiles per group
+  static constexpr int CPR = SW / 8;            // 16-B chunks per row of a group
+  static constexpr int CSH = SW == 32 ? 2 : 3;  // log2(CPR)
+  static constexpr int NI = 16 * CPR / 64;      // chunks per lane
+};
+// Group G and the ones after it, as straight-line code (compile-time recursion, not a loop).
+// One slab: row r of the wave's 16 is row `rowb + r` of dst (pitch ld), the head at column hoff,
+// and exists iff row0 + r < lim.
+template <int HD, bool TAIL, int G = 0>
+__device__ __forceinline__ void stage_out(short* slab, const f4v (&v)[HD / 16], bf16_t* dst, long rowb, long ld,
+                                          int hoff, int row0, int lim, int lane) {
+  using St = Stage<HD>;
+  if (G) __builtin_amdgcn_wave_barrier();  // the previous half's row reads precede these writes
+  slab_store(slab, reinterpret_cast<const f4v(&)[St::NT]>(v[G * St::NT]), lane);
+  __builtin_amdgcn_wave_barrier();
+#pragma unroll
+  for (int i = 0; i < St::NI; ++i) {
+    const int c = lane + i * 64;  // 16 rows x CPR chunks
+    const int r = c >> St::CSH, col = (c & (St::CPR - 1)) * 8;
+    if (!TAIL || row0 + r < lim)
+      *reinterpret_cast<s8v*>(dst + (rowb + r) * ld + hoff + G * St::SW + col) =
+          *reinterpret_cast<const s8v*>(slab + r * PLD + col);
+  }
+  if constexpr (G + 1 < St::NG) stage_out<HD, TAIL, G + 1>(slab, v, dst, rowb, ld, hoff, row0, lim, lane);
+}
+// Two slabs (dK, dV): drow = row 0 of the wave's 16 in the K half, the V half C columns on
+template <int HD, bool TAIL, int G = 0>
+__device__ __forceinline__ void stage_out2(short* pslab, short* dslab, const f4v (&dk)[HD / 16],
+                                           const f4v (&dv)[HD / 16], bf16_t* drow, long ld, int C, int row0, int lim,
+                                           int lane) {
+  using St = Stage<HD>;
+  if (G) __builtin_amdgcn_wave_barrier();
+  slab_store(pslab, reinterpret_cast<const f4v(&)[St::NT]>(dk[G * St::NT]), lane);
+  slab_store(dslab, reinterpret_cast<const f4v(&)[St::NT]>(dv[G * St::NT]), lane);
+  __builtin_amdgcn_wave_barrier();
+#pragma unroll
+  for (int i = 0; i < St::NI; ++i) {
+    const int c = lane + i * 64;
+    const int r = c >> St::CSH, col = (c & (St::CPR - 1)) * 8;
+    if (!TAIL || row0 + r < lim) {
+      *reinterpret_cast<s8v*>(drow + (long)r * ld + G * St::SW + col) =
+          *reinterpret_cast<const s8v*>(pslab + r * PLD + col);
+      *reinterpret_cast<s8v*>(drow + (long)r * ld + C + G * St::SW + col) =
+          *reinterpret_cast<const s8v*>(dslab + r * PLD + col);
+    }
+  }
+  if constexpr (G + 1 < St::NG) stage_out2<HD, TAIL, G + 1>(pslab, dslab, dk, dv, drow, ld, C, row0, lim, lane);
+}
+
+// The HD / 32 k-steps of a head-dim contraction, ascending, as compile-time recursion (each step's
+// offsets are constants, as in hand-unrolled code): the A fragments of a global row ...
+template <int NK, int KK = 0>
+__device__ __forceinline__ void gfrags(bf16x8* f, const bf16_t* rowp, int lane) {
+  f[KK] = gfrag(rowp, KK, lane);
+  if constexpr (KK + 1 < NK) gfrags<NK, KK + 1>(f, rowp, lane);
+}
+// ... and acc += A[kk] x (rows r0 .. r0 + 15 of a k-contiguous LDS tile at pitch LD)
+template <int LD, int NK, int KK = 0>
+__device__ __forceinline__ void mfma_hd(f4v& acc, const bf16x8* af, const short* lds, int r0, int lane) {
+  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[KK], frag_kc<LD>(lds, r0, KK * 32, lane), acc, 0, 0, 0);
+  if constexpr (KK + 1 < NK) mfma_hd<LD, NK, KK + 1>(acc, af, lds, r0, lane);
 }
 
 __device__ __forceinline__ float grp16_max(float v) {
@@ -150,10 +250,13 @@ struct AttnArgs {
   DropCfg drop;
 };
 
-// Dv[b,h,q] = sum_d dO[q, h*D+d] * O[q, h*D+d]: 8 lanes x 8 elements per (row, head)
+// Dv[b,h,q] = sum_d dO[q, h*HD+d] * O[q, h*HD+d]: HD / 8 lanes x 8 elements per (row, head),
+// 2048 / HD (row, head) pairs per workgroup
+template <int HD>
 __global__ void __launch_bounds__(256) attn_bwd_prep_kernel(AttnArgs a) {
-  const long g = (long)blockIdx.x * 32 + (threadIdx.x >> 3);
-  const int sub = threadIdx.x & 7;
+  constexpr int D = HD, LPR = HD / 8;
+  const long g = (long)blockIdx.x * (256 / LPR) + (threadIdx.x / LPR);
+  const int sub = threadIdx.x & (LPR - 1);
   const int H = a.H, S = a.S, C = H * D;
   const long rows = (long)a.B * S * H;
   if (g >= rows) return;
@@ -167,7 +270,8 @@ __global__ void __launch_bounds__(256) attn_bwd_prep_kernel(AttnArgs a) {
   for (int j = 0; j < 8; ++j) s += bf2f(uo[j]) * bf2f(ud[j]);
   s += __shfl_xor(s, 1, 64);
   s += __shfl_xor(s, 2, 64);
-  s += __shfl_xor(s, 4, 64);
+  if constexpr (LPR > 4) s += __shfl_xor(s, 4, 64);
+  if constexpr (LPR > 8) s += __shfl_xor(s, 8, 64);
   if (sub == 0) {
     const long b = row / S, q = row - b * S;
     a.dvec[(b * H + h) * S + q] = s;
@@ -301,11 +405,12 @@ __device__ __forceinline__ uint32_t mask_pack_k(const MaskRaw& m, int lane) {
   return bits;
 }
 
-template <bool TAIL, bool MASK, bool CAUSAL>
+template <int HD, bool TAIL, bool MASK, bool CAUSAL>
 __global__ void __launch_bounds__(256) attn_fwd_kernel(GenArgs a) {
   static_assert(!(MASK && CAUSAL), "a masked causal call carries the triangle in its mask");
-  __shared__ __attribute__((aligned(16))) short Ks[KB * LDT];
-  __shared__ __attribute__((aligned(16))) short Vs[KB * LDT];
+  constexpr int D = HD, LDH = HD + 8, NK = HD / 32, NO = HD / 16;  // k-steps of Q K^T, output tiles
+  __shared__ __attribute__((aligned(16))) short Ks[KB * LDH];
+  __shared__ __attribute__((aligned(16))) short Vs[KB * LDH];
   __shared__ __attribute__((aligned(16))) short Ps[4][16 * PLD];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int b = blockIdx.z, h = blockIdx.y;
@@ -317,14 +422,15 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(GenArgs a) {
   klen = klen < 1 ? 1 : (klen > S ? S : klen);
   const bf16_t* kbase = a.kv + (long)b * S * ldkv + h * D;
   const bf16_t* qrow = a.q + ((long)b * T + frag_row<TAIL>(q0 + (lane & 15), T)) * a.ldq + h * D;
-  const bf16x8 qf0 = gfrag(qrow, 0, lane), qf1 = gfrag(qrow, 1, lane);
+  bf16x8 qf[NK];
+  gfrags<NK>(qf, qrow, lane);
   const float c2 = a.scale * LOG2E;
   const long bh = (long)b * H + h;
   const uint64_t bhts = (uint64_t)bh * T * S;  // dropout index of element (q, key): bhts + q*S + key
   const uint8_t* mb = nullptr;
   if constexpr (MASK) mb = a.mask + b * a.msb + h * a.msh;
 
-  f4v o[4];
+  f4v o[NO];
   // causal: lr = the row sum of the probabilities as the P V product sees them (rounded to bf16).
   // The context is divided by lr, so its weights sum to one exactly; the log-sum-exp keeps the
   // unrounded sum l, which is what the backward recomputes P from.  A causal row has as few as one
@@ -333,7 +439,7 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(GenArgs a) {
   // S = 2 where dividing by lr leaves 7.6e-3.  The non-causal kernels divide by l.
   float m[4], l[4], lr[4];
 #pragma unroll
-  for (int t = 0; t < 4; ++t) o[t] = f4v{0.f, 0.f, 0.f, 0.f};
+  for (int t = 0; t < NO; ++t) o[t] = f4v{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     m[r] = -INFINITY;
@@ -348,8 +454,8 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(GenArgs a) {
     MaskRaw mraw;
     if constexpr (MASK) mraw = mask_load_q<TAIL>(mb, (uint32_t)a.mst, q0 + (lane >> 4) * 4, k0, T, S, lane);
     __syncthreads();
-    tile_load<TAIL>(Ks, kbase + (long)k0 * ldkv, ldkv, tid, S - k0);
-    tile_load<TAIL>(Vs, kbase + (long)k0 * ldkv + C, ldkv, tid, S - k0);
+    tile_load<TAIL, HD>(Ks, kbase + (long)k0 * ldkv, ldkv, tid, S - k0);
+    tile_load<TAIL, HD>(Vs, kbase + (long)k0 * ldkv + C, ldkv, tid, S - k0);
     uint32_t vis = 0;
     if constexpr (MASK) vis = mask_pack_q(mraw);  // here: the mask bytes arrive before the tile's
     __syncthreads();
@@ -358,8 +464,7 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(GenArgs a) {
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
       s[t] = f4v{0.f, 0.f, 0.f, 0.f};
-      s[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf0, read_frag<64, true>(Ks, t * 16, 0, lane), s[t], 0, 0, 0);
-      s[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf1, read_frag<64, true>(Ks, t * 16, 32, lane), s[t], 0, 0, 0);
+      mfma_hd<LDH, NK>(s[t], qf, Ks, t * 16, lane);
     }
     float alpha[4];
 #pragma unroll
@@ -409,16 +514,16 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(GenArgs a) {
         }
     }
 #pragma unroll
-    for (int t = 0; t < 4; ++t)
+    for (int t = 0; t < NO; ++t)
 #pragma unroll
       for (int r = 0; r < 4; ++r) o[t][r] *= alpha[r];
     slab_store(slab, s, lane);
     __builtin_amdgcn_wave_barrier();
     const bf16x8 p0 = slab_frag(slab, 0, lane), p1 = slab_frag(slab, 1, lane);
 #pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      o[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(p0, read_frag<64, false>(Vs, t * 16, 0, lane), o[t], 0, 0, 0);
-      o[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(p1, read_frag<64, false>(Vs, t * 16, 32, lane), o[t], 0, 0, 0);
+    for (int t = 0; t < NO; ++t) {
+      o[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(p0, frag_nc<LDH>(Vs, t * 16, 0, lane), o[t], 0, 0, 0);
+      o[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(p1, frag_nc<LDH>(Vs, t * 16, 32, lane), o[t], 0, 0, 0);
     }
     __builtin_amdgcn_wave_barrier();
   }
@@ -434,29 +539,34 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(GenArgs a) {
     }
     if ((lane & 15) == 0 && (!TAIL || q0 + (lane >> 4) * 4 + r < T)) a.lse[bh * T + q0 + (lane >> 4) * 4 + r] = lse;
   }
-  // normalise, stage through the wave slab, 16-B row stores
+  // normalise, stage through the wave slab (Stage<HD>: 64-column halves at HD = 128), 16-B row stores
 #pragma unroll
-  for (int t = 0; t < 4; ++t)
+  for (int t = 0; t < NO; ++t)
 #pragma unroll
     for (int r = 0; r < 4; ++r) o[t][r] *= inv[r];
-  slab_store(slab, o, lane);
-  __builtin_amdgcn_wave_barrier();
+  if constexpr (HD == 64) {  // the one-group case, written out
+    slab_store(slab, o, lane);
+    __builtin_amdgcn_wave_barrier();
 #pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int c = lane + i * 64;  // 16 rows x 8 chunks
-    const int r = c >> 3, col = (c & 7) * 8;
-    if (!TAIL || q0 + r < T)
-      *reinterpret_cast<s8v*>(a.ctx + ((long)b * T + q0 + r) * C + h * D + col) =
-          *reinterpret_cast<const s8v*>(slab + r * PLD + col);
+    for (int i = 0; i < 2; ++i) {
+      const int c = lane + i * 64;  // 16 rows x 8 chunks
+      const int r = c >> 3, col = (c & 7) * 8;
+      if (!TAIL || q0 + r < T)
+        *reinterpret_cast<s8v*>(a.ctx + ((long)b * T + q0 + r) * C + h * D + col) =
+            *reinterpret_cast<const s8v*>(slab + r * PLD + col);
+    }
+  } else {
+    stage_out<HD, TAIL>(slab, o, a.ctx, (long)b * T + q0, C, h * D, q0, T, lane);
   }
 }
 
 // grid: ceil(S / 64) key blocks; rows of keys >= key_len[b] are stored as exact zeros
-template <bool TAIL, bool MASK, bool CAUSAL>
+template <int HD, bool TAIL, bool MASK, bool CAUSAL>
 __global__ void __launch_bounds__(256) attn_bwd_dkv_kernel(GenArgs a) {
   static_assert(!(MASK && CAUSAL), "a masked causal call carries the triangle in its mask");
-  __shared__ __attribute__((aligned(16))) short Qs[QB * LDT];
-  __shared__ __attribute__((aligned(16))) short Gs[QB * LDT];  // dO
+  constexpr int D = HD, LDH = HD + 8, NK = HD / 32, NO = HD / 16;  // k-steps of K Q^T / V dO^T, dK / dV tiles
+  __shared__ __attribute__((aligned(16))) short Qs[QB * LDH];
+  __shared__ __attribute__((aligned(16))) short Gs[QB * LDH];  // dO
   __shared__ __attribute__((aligned(16))) short Ps[4][16 * PLD];
   __shared__ __attribute__((aligned(16))) short Ds[4][16 * PLD];
   __shared__ float lse_s[QB], dv_s[QB];
@@ -474,12 +584,13 @@ __global__ void __launch_bounds__(256) attn_bwd_dkv_kernel(GenArgs a) {
   const bf16_t* gbase = a.dout + (long)b * T * C + h * D;
   const bf16_t* krow = a.kv + ((long)b * S + frag_row<TAIL>(k0 + (lane & 15), S)) * ldkv + h * D;
   const bf16_t* vrow = krow + C;
-  const bf16x8 kf0 = gfrag(krow, 0, lane), kf1 = gfrag(krow, 1, lane);
-  const bf16x8 vf0 = gfrag(vrow, 0, lane), vf1 = gfrag(vrow, 1, lane);
+  bf16x8 kf[NK], vf[NK];
+  gfrags<NK>(kf, krow, lane);
+  gfrags<NK>(vf, vrow, lane);
   const float c2 = a.scale * LOG2E;
-  f4v dk[4], dv[4];
+  f4v dk[NO], dv[NO];
 #pragma unroll
-  for (int t = 0; t < 4; ++t) dk[t] = dv[t] = f4v{0.f, 0.f, 0.f, 0.f};
+  for (int t = 0; t < NO; ++t) dk[t] = dv[t] = f4v{0.f, 0.f, 0.f, 0.f};
   short* pslab = Ps[wave];
   short* dslab = Ds[wave];
   const bool any_valid = (uint32_t)bx * KB < (uint32_t)klen;
@@ -493,8 +604,8 @@ __global__ void __launch_bounds__(256) attn_bwd_dkv_kernel(GenArgs a) {
     MaskRaw mraw;
     if constexpr (MASK) mraw = mask_load_k<TAIL>(mb, (uint32_t)a.mst, q0, k0, T, S, lane);
     __syncthreads();
-    tile_load<TAIL>(Qs, qbase + (long)q0 * ldq, ldq, tid, T - q0);
-    tile_load<TAIL>(Gs, gbase + (long)q0 * C, C, tid, T - q0);
+    tile_load<TAIL, HD>(Qs, qbase + (long)q0 * ldq, ldq, tid, T - q0);
+    tile_load<TAIL, HD>(Gs, gbase + (long)q0 * C, C, tid, T - q0);
     if (tid < QB) {
       const bool live = !TAIL || q0 + tid < T;  // queries >= T: no lse / Dv entry exists
       lse_s[tid] = live ? a.lse[bh * T + q0 + tid] : 0.f;
@@ -508,11 +619,9 @@ __global__ void __launch_bounds__(256) attn_bwd_dkv_kernel(GenArgs a) {
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
       p[t] = f4v{0.f, 0.f, 0.f, 0.f};
-      p[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf0, read_frag<64, true>(Qs, t * 16, 0, lane), p[t], 0, 0, 0);
-      p[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf1, read_frag<64, true>(Qs, t * 16, 32, lane), p[t], 0, 0, 0);
+      mfma_hd<LDH, NK>(p[t], kf, Qs, t * 16, lane);
       dp[t] = f4v{0.f, 0.f, 0.f, 0.f};
-      dp[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf0, read_frag<64, true>(Gs, t * 16, 0, lane), dp[t], 0, 0, 0);
-      dp[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf1, read_frag<64, true>(Gs, t * 16, 32, lane), dp[t], 0, 0, 0);
+      mfma_hd<LDH, NK>(dp[t], vf, Gs, t * 16, lane);
     }
     f4v pd[4], ds[4];
 #pragma unroll
@@ -540,32 +649,37 @@ __global__ void __launch_bounds__(256) attn_bwd_dkv_kernel(GenArgs a) {
     const bf16x8 pa0 = slab_frag(pslab, 0, lane), pa1 = slab_frag(pslab, 1, lane);
     const bf16x8 da0 = slab_frag(dslab, 0, lane), da1 = slab_frag(dslab, 1, lane);
 #pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      dv[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pa0, read_frag<64, false>(Gs, t * 16, 0, lane), dv[t], 0, 0, 0);
-      dv[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pa1, read_frag<64, false>(Gs, t * 16, 32, lane), dv[t], 0, 0, 0);
-      dk[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(da0, read_frag<64, false>(Qs, t * 16, 0, lane), dk[t], 0, 0, 0);
-      dk[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(da1, read_frag<64, false>(Qs, t * 16, 32, lane), dk[t], 0, 0, 0);
+    for (int t = 0; t < NO; ++t) {
+      dv[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pa0, frag_nc<LDH>(Gs, t * 16, 0, lane), dv[t], 0, 0, 0);
+      dv[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pa1, frag_nc<LDH>(Gs, t * 16, 32, lane), dv[t], 0, 0, 0);
+      dk[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(da0, frag_nc<LDH>(Qs, t * 16, 0, lane), dk[t], 0, 0, 0);
+      dk[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(da1, frag_nc<LDH>(Qs, t * 16, 32, lane), dk[t], 0, 0, 0);
     }
     __builtin_amdgcn_wave_barrier();
   }
 #pragma unroll
-  for (int t = 0; t < 4; ++t)
+  for (int t = 0; t < NO; ++t)
 #pragma unroll
     for (int r = 0; r < 4; ++r) dk[t][r] *= a.scale;
-  // stage through the slabs -> 16-B stores into dkv (K and V halves)
-  slab_store(pslab, dk, lane);
-  slab_store(dslab, dv, lane);
-  __builtin_amdgcn_wave_barrier();
-  bf16_t* drow = a.dkv + ((long)b * S + k0) * lddkv + h * D;
+  // stage through the slabs (Stage<HD>) -> 16-B stores into dkv (K and V halves)
+  if constexpr (HD == 64) {  // the one-group case, written out
+    slab_store(pslab, dk, lane);
+    slab_store(dslab, dv, lane);
+    __builtin_amdgcn_wave_barrier();
+    bf16_t* drow = a.dkv + ((long)b * S + k0) * lddkv + h * D;
 #pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int c = lane + i * 64;
-    const int r = c >> 3, col = (c & 7) * 8;
-    if (!TAIL || k0 + r < S) {
-      *reinterpret_cast<s8v*>(drow + (long)r * lddkv + col) = *reinterpret_cast<const s8v*>(pslab + r * PLD + col);
-      *reinterpret_cast<s8v*>(drow + (long)r * lddkv + C + col) =
-          *reinterpret_cast<const s8v*>(dslab + r * PLD + col);
+    for (int i = 0; i < 2; ++i) {
+      const int c = lane + i * 64;
+      const int r = c >> 3, col = (c & 7) * 8;
+      if (!TAIL || k0 + r < S) {
+        *reinterpret_cast<s8v*>(drow + (long)r * lddkv + col) = *reinterpret_cast<const s8v*>(pslab + r * PLD + col);
+        *reinterpret_cast<s8v*>(drow + (long)r * lddkv + C + col) =
+            *reinterpret_cast<const s8v*>(dslab + r * PLD + col);
+      }
     }
+  } else {
+    bf16_t* drow = a.dkv + ((long)b * S + k0) * lddkv + h * D;
+    stage_out2<HD, TAIL>(pslab, dslab, dk, dv, drow, lddkv, C, k0, S, lane);
   }
 }
 
@@ -574,11 +688,17 @@ __global__ void __launch_bounds__(256) attn_bwd_dkv_kernel(GenArgs a) {
 // 141 + 32 = 173) and run two; asked, every instantiation fits in 162 or fewer without scratch.
 // The plain non-tail one reaches three waves unasked (136 + 32) but is 4 - 5 % faster per forward +
 // backward call with the request (156 + 0): docs/performance.md, "One generic attention kernel family".
-template <bool TAIL, bool MASK, bool CAUSAL>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) attn_bwd_dq_kernel(GenArgs a) {
+// That is HD = 64, and HD = 32 takes the same request (it fits in 130 or fewer).  HD = 128 carries 8 dQ
+// tiles and 4 + 4 fragment registers: asked for three waves it spills (16 - 72 bytes per lane), asked for
+// two it fits in 198 or fewer without scratch (docs/performance.md, "Attention head dimensions").
+template <int HD>
+constexpr int DQ_WAVES = HD == 128 ? 2 : 3;
+template <int HD, bool TAIL, bool MASK, bool CAUSAL>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DQ_WAVES<HD>))) attn_bwd_dq_kernel(GenArgs a) {
   static_assert(!(MASK && CAUSAL), "a masked causal call carries the triangle in its mask");
-  __shared__ __attribute__((aligned(16))) short Ks[KB * LDT];
-  __shared__ __attribute__((aligned(16))) short Vs[KB * LDT];
+  constexpr int D = HD, LDH = HD + 8, NK = HD / 32, NO = HD / 16;  // k-steps of Q K^T / dO V^T, dQ tiles
+  __shared__ __attribute__((aligned(16))) short Ks[KB * LDH];
+  __shared__ __attribute__((aligned(16))) short Vs[KB * LDH];
   __shared__ __attribute__((aligned(16))) short Ds[4][16 * PLD];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int b = blockIdx.z, h = blockIdx.y;
@@ -594,8 +714,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) a
   const long qr = (long)b * T + frag_row<TAIL>(q0 + (lane & 15), T);
   const bf16_t* qrow = a.q + qr * a.ldq + h * D;
   const bf16_t* grow = a.dout + qr * C + h * D;
-  const bf16x8 qf0 = gfrag(qrow, 0, lane), qf1 = gfrag(qrow, 1, lane);
-  const bf16x8 gf0 = gfrag(grow, 0, lane), gf1 = gfrag(grow, 1, lane);
+  bf16x8 qf[NK], gf[NK];
+  gfrags<NK>(qf, qrow, lane);
+  gfrags<NK>(gf, grow, lane);
   const float c2 = a.scale * LOG2E;
   float ls[4], dvq[4];
 #pragma unroll
@@ -606,9 +727,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) a
   }
   const uint8_t* mb = nullptr;
   if constexpr (MASK) mb = a.mask + b * a.msb + h * a.msh;
-  f4v dq[4];
+  f4v dq[NO];
 #pragma unroll
-  for (int t = 0; t < 4; ++t) dq[t] = f4v{0.f, 0.f, 0.f, 0.f};
+  for (int t = 0; t < NO; ++t) dq[t] = f4v{0.f, 0.f, 0.f, 0.f};
   short* dslab = Ds[wave];
   int nkb = (klen + KB - 1) / KB;  // key blocks entirely past key_len are not read
   // causal: key blocks past the diagonal one (QB == KB) are entirely in the future
@@ -618,8 +739,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) a
     MaskRaw mraw;
     if constexpr (MASK) mraw = mask_load_q<TAIL>(mb, (uint32_t)a.mst, q0 + (lane >> 4) * 4, k0, T, S, lane);
     __syncthreads();
-    tile_load<TAIL>(Ks, kbase + (long)k0 * ldkv, ldkv, tid, S - k0);
-    tile_load<TAIL>(Vs, kbase + (long)k0 * ldkv + C, ldkv, tid, S - k0);
+    tile_load<TAIL, HD>(Ks, kbase + (long)k0 * ldkv, ldkv, tid, S - k0);
+    tile_load<TAIL, HD>(Vs, kbase + (long)k0 * ldkv + C, ldkv, tid, S - k0);
     uint32_t vis = 0;
     if constexpr (MASK) vis = mask_pack_q(mraw);  // here: the mask bytes arrive before the tile's
     __syncthreads();
@@ -628,11 +749,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) a
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
       s[t] = f4v{0.f, 0.f, 0.f, 0.f};
-      s[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf0, read_frag<64, true>(Ks, t * 16, 0, lane), s[t], 0, 0, 0);
-      s[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf1, read_frag<64, true>(Ks, t * 16, 32, lane), s[t], 0, 0, 0);
+      mfma_hd<LDH, NK>(s[t], qf, Ks, t * 16, lane);
       dp[t] = f4v{0.f, 0.f, 0.f, 0.f};
-      dp[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(gf0, read_frag<64, true>(Vs, t * 16, 0, lane), dp[t], 0, 0, 0);
-      dp[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(gf1, read_frag<64, true>(Vs, t * 16, 32, lane), dp[t], 0, 0, 0);
+      mfma_hd<LDH, NK>(dp[t], gf, Vs, t * 16, lane);
     }
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
@@ -652,25 +771,29 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) a
     __builtin_amdgcn_wave_barrier();
     const bf16x8 d0 = slab_frag(dslab, 0, lane), d1 = slab_frag(dslab, 1, lane);
 #pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      dq[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(d0, read_frag<64, false>(Ks, t * 16, 0, lane), dq[t], 0, 0, 0);
-      dq[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(d1, read_frag<64, false>(Ks, t * 16, 32, lane), dq[t], 0, 0, 0);
+    for (int t = 0; t < NO; ++t) {
+      dq[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(d0, frag_nc<LDH>(Ks, t * 16, 0, lane), dq[t], 0, 0, 0);
+      dq[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(d1, frag_nc<LDH>(Ks, t * 16, 32, lane), dq[t], 0, 0, 0);
     }
     __builtin_amdgcn_wave_barrier();
   }
 #pragma unroll
-  for (int t = 0; t < 4; ++t)
+  for (int t = 0; t < NO; ++t)
 #pragma unroll
     for (int r = 0; r < 4; ++r) dq[t][r] *= a.scale;
-  slab_store(dslab, dq, lane);
-  __builtin_amdgcn_wave_barrier();
+  if constexpr (HD == 64) {  // the one-group case, written out
+    slab_store(dslab, dq, lane);
+    __builtin_amdgcn_wave_barrier();
 #pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int c = lane + i * 64;
-    const int r = c >> 3, col = (c & 7) * 8;
-    if (!TAIL || q0 + r < T)
-      *reinterpret_cast<s8v*>(a.dq + ((long)b * T + q0 + r) * a.lddq + h * D + col) =
-          *reinterpret_cast<const s8v*>(dslab + r * PLD + col);
+    for (int i = 0; i < 2; ++i) {
+      const int c = lane + i * 64;
+      const int r = c >> 3, col = (c & 7) * 8;
+      if (!TAIL || q0 + r < T)
+        *reinterpret_cast<s8v*>(a.dq + ((long)b * T + q0 + r) * a.lddq + h * D + col) =
+            *reinterpret_cast<const s8v*>(dslab + r * PLD + col);
+    }
+  } else {
+    stage_out<HD, TAIL>(dslab, dq, a.dq, (long)b * T + q0, a.lddq, h * D, q0, T, lane);
   }
 }
 
@@ -687,21 +810,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) a
 // Every P / dS element is computed (and its dropout bit hashed) once instead of twice.
 // LDS: 2 x [S][72] + [S][S + 8] bf16 = 72 KB at S = 128 (two 8-wave blocks per CU; the
 // first version kept K, P and dS in separate arrays, 124 KB, one block per CU: 37-38 us).
-template <int LD>
-__device__ __forceinline__ bf16x8 frag_kc(const short* lds, int r0, int k0, int lane) {
-  s8v v = *reinterpret_cast<const s8v*>(lds + (r0 + (lane & 15)) * LD + k0 + 8 * (lane >> 4));
-  return __builtin_bit_cast(bf16x8, v);
-}
-// element (r, k) at lds[k * LD + r] (r contiguous): the transposed read
-template <int LD>
-__device__ __forceinline__ bf16x8 frag_nc(const short* lds, int r0, int k0, int lane) {
-  const int g = lane >> 4, q = (lane & 15) >> 2, p = lane & 3;
-  const short* b0 = lds + (k0 + 8 * g + q) * LD + r0 + 4 * p;
-  s4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4v*)(b0));
-  s4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4v*)(b0 + 4 * LD));
-  s8v v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8, v);
-}
 
 // C-layout 16 x 64 fp32 (4 column tiles, lane l: row 4 (l >> 4) + r, column 16 t + (l & 15))
 // -> bf16 [16][LDT] slab, then 16-B row stores to dst rows (pitch ld)
@@ -1024,8 +1132,8 @@ void cross_set_mask(GenArgs& a, const uint8_t* mask, long sb, long sh, long st) 
 }
 // The generic kernels' view of a packed-qkv call: Q and K | V, and their gradients, are column
 // ranges of rows at pitch 3C
-GenArgs self_args(const AttnArgs& s) {
-  const int C = s.H * D;
+GenArgs self_args(const AttnArgs& s, int hd) {
+  const int C = s.H * hd;
   GenArgs a{};
   a.q = s.qkv; a.kv = s.qkv + C; a.dout = s.dout; a.ctx = s.ctx; a.dq = s.dqkv;
   a.dkv = s.dqkv ? s.dqkv + C : nullptr;  // forward: no gradients
@@ -1040,20 +1148,47 @@ static_assert(QB == KB, "causal: one grid for the key-block and the query-block 
 bool gen_tail(const GenArgs& a) { return a.T % QB != 0 || a.S % KB != 0; }
 dim3 gen_qgrid(const GenArgs& a) { return dim3((a.T + QB - 1) / QB, a.H, a.B); }
 dim3 gen_kgrid(const GenArgs& a) { return dim3((a.S + KB - 1) / KB, a.H, a.B); }
+template <int HD, bool MASK, bool CAUSAL>
+void launch_fwd_hd(const GenArgs& a, hipStream_t s) {
+  if (gen_tail(a)) attn_fwd_kernel<HD, true, MASK, CAUSAL><<<gen_qgrid(a), 256, 0, s>>>(a);
+  else attn_fwd_kernel<HD, false, MASK, CAUSAL><<<gen_qgrid(a), 256, 0, s>>>(a);
+}
+template <int HD, bool MASK, bool CAUSAL>
+void launch_bwd_dkv_hd(const GenArgs& a, hipStream_t s) {
+  if (gen_tail(a)) attn_bwd_dkv_kernel<HD, true, MASK, CAUSAL><<<gen_kgrid(a), 256, 0, s>>>(a);
+  else attn_bwd_dkv_kernel<HD, false, MASK, CAUSAL><<<gen_kgrid(a), 256, 0, s>>>(a);
+}
+template <int HD, bool MASK, bool CAUSAL>
+void launch_bwd_dq_hd(const GenArgs& a, hipStream_t s) {
+  if (gen_tail(a)) attn_bwd_dq_kernel<HD, true, MASK, CAUSAL><<<gen_qgrid(a), 256, 0, s>>>(a);
+  else attn_bwd_dq_kernel<HD, false, MASK, CAUSAL><<<gen_qgrid(a), 256, 0, s>>>(a);
+}
+// Head-dim dispatch; hd is one of the supported widths (head_dim_ok, checked by every entry point)
+bool head_dim_ok(int hd) { return hd == 32 || hd == 64 || hd == 128; }
 template <bool MASK, bool CAUSAL>
-void launch_fwd(const GenArgs& a, hipStream_t s) {
-  if (gen_tail(a)) attn_fwd_kernel<true, MASK, CAUSAL><<<gen_qgrid(a), 256, 0, s>>>(a);
-  else attn_fwd_kernel<false, MASK, CAUSAL><<<gen_qgrid(a), 256, 0, s>>>(a);
+void launch_fwd(const GenArgs& a, int hd, hipStream_t s) {
+  if (hd == 32) launch_fwd_hd<32, MASK, CAUSAL>(a, s);
+  else if (hd == 128) launch_fwd_hd<128, MASK, CAUSAL>(a, s);
+  else launch_fwd_hd<64, MASK, CAUSAL>(a, s);
 }
 template <bool MASK, bool CAUSAL>
-void launch_bwd_dkv(const GenArgs& a, hipStream_t s) {
-  if (gen_tail(a)) attn_bwd_dkv_kernel<true, MASK, CAUSAL><<<gen_kgrid(a), 256, 0, s>>>(a);
-  else attn_bwd_dkv_kernel<false, MASK, CAUSAL><<<gen_kgrid(a), 256, 0, s>>>(a);
+void launch_bwd_dkv(const GenArgs& a, int hd, hipStream_t s) {
+  if (hd == 32) launch_bwd_dkv_hd<32, MASK, CAUSAL>(a, s);
+  else if (hd == 128) launch_bwd_dkv_hd<128, MASK, CAUSAL>(a, s);
+  else launch_bwd_dkv_hd<64, MASK, CAUSAL>(a, s);
 }
 template <bool MASK, bool CAUSAL>
-void launch_bwd_dq(const GenArgs& a, hipStream_t s) {
-  if (gen_tail(a)) attn_bwd_dq_kernel<true, MASK, CAUSAL><<<gen_qgrid(a), 256, 0, s>>>(a);
-  else attn_bwd_dq_kernel<false, MASK, CAUSAL><<<gen_qgrid(a), 256, 0, s>>>(a);
+void launch_bwd_dq(const GenArgs& a, int hd, hipStream_t s) {
+  if (hd == 32) launch_bwd_dq_hd<32, MASK, CAUSAL>(a, s);
+  else if (hd == 128) launch_bwd_dq_hd<128, MASK, CAUSAL>(a, s);
+  else launch_bwd_dq_hd<64, MASK, CAUSAL>(a, s);
+}
+// Dv = rowsum(dO * O) over a.B * a.S query rows of a.H heads
+void launch_prep(const AttnArgs& a, int hd, hipStream_t s) {
+  const long pairs = (long)a.B * a.S * a.H;
+  if (hd == 32) attn_bwd_prep_kernel<32><<<ca_cdiv(pairs, 64), 256, 0, s>>>(a);
+  else if (hd == 128) attn_bwd_prep_kernel<128><<<ca_cdiv(pairs, 16), 256, 0, s>>>(a);
+  else attn_bwd_prep_kernel<64><<<ca_cdiv(pairs, 32), 256, 0, s>>>(a);
 }
 
 // CLOUD_AMD_ATTN_FUSED_BWD=0 keeps the three-kernel backward at S <= 128 (A/B runs)
@@ -1072,91 +1207,90 @@ extern "C" {
 
 // ctx = softmax(Q K^T * scale + keymask) (dropout) V ; lse[B][H][S] saved for the backward.
 // causal != 0: key j is visible to query i iff j <= i (and j < key_len[b]).
-int ca_attn_fwd(const bf16_t* qkv, bf16_t* ctx, float* lse, const int* key_len, int B, int S, int H, float scale,
-                float p_drop, uint64_t seed, int causal, hipStream_t s) {
-  if (!shape_ok(S, H)) return -1;
+int ca_attn_fwd(const bf16_t* qkv, bf16_t* ctx, float* lse, const int* key_len, int B, int S, int H, int hd,
+                float scale, float p_drop, uint64_t seed, int causal, hipStream_t s) {
+  if (!shape_ok(S, H) || !head_dim_ok(hd)) return -1;
   AttnArgs a{};
   a.qkv = qkv; a.ctx = ctx; a.lse = lse; a.key_len = key_len;
   a.B = B; a.S = S; a.H = H; a.scale = scale; a.drop = make_drop(p_drop, seed);
-  if ((S == 64 || S == 128) && fused_bwd_enabled()) {
+  if ((S == 64 || S == 128) && hd == D && fused_bwd_enabled()) {
     if (causal) launch_fwd_short<true>(a, s);
     else launch_fwd_short<false>(a, s);
     CA_LAUNCH_CHECK();
     return 0;
   }
-  if (causal) launch_fwd<false, true>(self_args(a), s);
-  else launch_fwd<false, false>(self_args(a), s);
+  if (causal) launch_fwd<false, true>(self_args(a, hd), hd, s);
+  else launch_fwd<false, false>(self_args(a, hd), hd, s);
   CA_LAUNCH_CHECK();
   return 0;
 }
 
 // dqkv (all three thirds written) from dctx; dvec: [B][H][S] fp32 scratch.
 int ca_attn_bwd(const bf16_t* qkv, const bf16_t* out, const bf16_t* dout, const float* lse, float* dvec,
-                bf16_t* dqkv, const int* key_len, int B, int S, int H, float scale, float p_drop, uint64_t seed,
-                int causal, hipStream_t s) {
-  if (!shape_ok(S, H)) return -1;
+                bf16_t* dqkv, const int* key_len, int B, int S, int H, int hd, float scale, float p_drop,
+                uint64_t seed, int causal, hipStream_t s) {
+  if (!shape_ok(S, H) || !head_dim_ok(hd)) return -1;
   AttnArgs a{};
   a.qkv = qkv; a.out = out; a.dout = dout; a.lse = const_cast<float*>(lse); a.dvec = dvec; a.dqkv = dqkv;
   a.key_len = key_len; a.B = B; a.S = S; a.H = H; a.scale = scale; a.drop = make_drop(p_drop, seed);
-  if ((S == 64 || S == 128) && fused_bwd_enabled()) {
+  if ((S == 64 || S == 128) && hd == D && fused_bwd_enabled()) {
     if (causal) launch_bwd_fused<true>(a, s);
     else launch_bwd_fused<false>(a, s);
     CA_LAUNCH_CHECK();
     return 0;
   }
-  const long rows = (long)B * S * H;
-  attn_bwd_prep_kernel<<<ca_cdiv(rows, 32), 256, 0, s>>>(a);
+  launch_prep(a, hd, s);
   CA_LAUNCH_CHECK();
-  const GenArgs g = self_args(a);
-  if (causal) launch_bwd_dkv<false, true>(g, s);
-  else launch_bwd_dkv<false, false>(g, s);
+  const GenArgs g = self_args(a, hd);
+  if (causal) launch_bwd_dkv<false, true>(g, hd, s);
+  else launch_bwd_dkv<false, false>(g, hd, s);
   CA_LAUNCH_CHECK();
-  if (causal) launch_bwd_dq<false, true>(g, s);
-  else launch_bwd_dq<false, false>(g, s);
+  if (causal) launch_bwd_dq<false, true>(g, hd, s);
+  else launch_bwd_dq<false, false>(g, hd, s);
   CA_LAUNCH_CHECK();
   return 0;
 }
 
-// Cross-attention: ctx[B*T][H*64] = softmax(Q K^T * scale + keymask) (dropout) V for q rows at pitch
+// Cross-attention (head dim hd): ctx[B*T][H*hd] = softmax(Q K^T * scale + keymask) (dropout) V for q rows at pitch
 // ldq and kv = K | V rows at pitch ldkv (elements; multiples of 8, 16-byte aligned bases);
 // lse[B][H][T] saved for the backward.
 // mask (null = none): byte (b, h, q, key) at b*msb + h*msh + q*mst + key, element strides, 0 = broadcast;
 // a score takes part iff key < key_len[b] and its byte is non-zero.  A query that sees no key gets
 // context 0 and lse 0, and contributes 0 to every gradient.
 int ca_attn_cross_fwd(const bf16_t* q, const bf16_t* kv, bf16_t* ctx, float* lse, const int* key_len,
-                      const uint8_t* mask, long msb, long msh, long mst, int B, int T, int S, int H, long ldq,
+                      const uint8_t* mask, long msb, long msh, long mst, int B, int T, int S, int H, int hd, long ldq,
                       long ldkv, float scale, float p_drop, uint64_t seed, hipStream_t s) {
-  if (!cross_shape_ok(B, T, S, H) || !cross_mask_ok(mask, msb, msh, mst, T, S)) return -1;
+  if (!cross_shape_ok(B, T, S, H) || !head_dim_ok(hd) || !cross_mask_ok(mask, msb, msh, mst, T, S)) return -1;
   GenArgs a{};
   a.q = q; a.kv = kv; a.ctx = ctx; a.lse = lse; a.key_len = key_len; a.ldq = ldq; a.ldkv = ldkv;
   a.B = B; a.T = T; a.S = S; a.H = H; a.scale = scale; a.drop = make_drop(p_drop, seed);
   cross_set_mask(a, mask, msb, msh, mst);
-  if (mask) launch_fwd<true, false>(a, s);
-  else launch_fwd<false, false>(a, s);
+  if (mask) launch_fwd<true, false>(a, hd, s);
+  else launch_fwd<false, false>(a, hd, s);
   CA_LAUNCH_CHECK();
   return 0;
 }
 
-// dq[B*T][H*64] and dkv[B*S][2*H*64] (every row written) from dctx; dvec: [B][H][T] fp32 scratch.
+// dq[B*T][H*hd] and dkv[B*S][2*H*hd] (every row written) from dctx; dvec: [B][H][T] fp32 scratch.
 int ca_attn_cross_bwd(const bf16_t* q, const bf16_t* kv, const bf16_t* out, const bf16_t* dout, const float* lse,
                       float* dvec, bf16_t* dq, bf16_t* dkv, const int* key_len, const uint8_t* mask, long msb,
-                      long msh, long mst, int B, int T, int S, int H, long ldq, long ldkv, float scale, float p_drop,
-                      uint64_t seed, hipStream_t s) {
-  if (!cross_shape_ok(B, T, S, H) || !cross_mask_ok(mask, msb, msh, mst, T, S)) return -1;
+                      long msh, long mst, int B, int T, int S, int H, int hd, long ldq, long ldkv, float scale,
+                      float p_drop, uint64_t seed, hipStream_t s) {
+  if (!cross_shape_ok(B, T, S, H) || !head_dim_ok(hd) || !cross_mask_ok(mask, msb, msh, mst, T, S)) return -1;
   AttnArgs p{};  // Dv = rowsum(dO * O) over the B*T query rows
   p.out = out; p.dout = dout; p.dvec = dvec; p.B = B; p.S = T; p.H = H;
-  attn_bwd_prep_kernel<<<ca_cdiv((long)B * T * H, 32), 256, 0, s>>>(p);
+  launch_prep(p, hd, s);
   CA_LAUNCH_CHECK();
   GenArgs a{};
   a.q = q; a.kv = kv; a.dout = dout; a.lse = const_cast<float*>(lse); a.dvec = dvec; a.dq = dq; a.dkv = dkv;
-  a.key_len = key_len; a.ldq = ldq; a.ldkv = ldkv; a.lddq = (long)H * D; a.lddkv = 2L * H * D;
+  a.key_len = key_len; a.ldq = ldq; a.ldkv = ldkv; a.lddq = (long)H * hd; a.lddkv = 2L * H * hd;
   a.B = B; a.T = T; a.S = S; a.H = H; a.scale = scale; a.drop = make_drop(p_drop, seed);
   cross_set_mask(a, mask, msb, msh, mst);
-  if (mask) launch_bwd_dkv<true, false>(a, s);
-  else launch_bwd_dkv<false, false>(a, s);
+  if (mask) launch_bwd_dkv<true, false>(a, hd, s);
+  else launch_bwd_dkv<false, false>(a, hd, s);
   CA_LAUNCH_CHECK();
-  if (mask) launch_bwd_dq<true, false>(a, s);
-  else launch_bwd_dq<false, false>(a, s);
+  if (mask) launch_bwd_dq<true, false>(a, hd, s);
+  else launch_bwd_dq<false, false>(a, hd, s);
   CA_LAUNCH_CHECK();
   return 0;
 }
