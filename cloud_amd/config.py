@@ -57,6 +57,11 @@ _VARS = [
     Var("CLOUD_AMD_DETERMINISTIC", bool, False, "raise instead of taking an order-dependent float-atomic kernel "
         "path (embedding gradient with more than two token types or rows wider than the owner kernel holds)",
         "ops"),
+    Var("CLOUD_AMD_XENT_VOCAB_MIN_C", int, 1010, "softmax cross-entropy past the one-block batch kernel: rows at "
+        "least this wide run on the one-row-per-workgroup kernels of csrc/kernels/xent_vocab.hip, narrower ones "
+        "(classifier heads up to 1009 classes) on the one-wave-per-row kernel; bench/xent_vocab.py, measured in "
+        "docs/performance.md: not slower from 1010 on (1024 x 1010: 0.98, 65536 x 1010: 0.78 of the row kernel's time)",
+        "ops"),
     Var("CLOUD_AMD_GEMM", str, "native", "dense GEMMs: 'native' or 'torch'", "ops"),
     Var("CLOUD_AMD_CONV", str, "native", "convolutions: 'native' or 'torch'", "ops"),
     Var("CLOUD_AMD_GEMM_CORE", str, "auto", "GEMM core: 'auto' (128x128 LDS-DMA core plus the 256x256 two-phase "

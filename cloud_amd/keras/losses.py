@@ -48,8 +48,19 @@ class Loss:
             y_true = torch.as_tensor(y_true).to(y_pred.device)
         per = self.per_example(y_true, y_pred)
         if sample_weight is not None:
-            per = per * torch.as_tensor(sample_weight, device=per.device, dtype=per.dtype)
+            w = torch.as_tensor(sample_weight, device=per.device, dtype=per.dtype)
+            if w.dim() == 1 and per.dim() > 1:  # [B] weights over a [B, T, ...] loss
+                w = w.reshape((-1,) + (1,) * (per.dim() - 1))
+            per = per * w
+        kept = self.valid_mask(y_true)
+        if kept is not None and self.reduction in (Reduction.AUTO, Reduction.SUM_OVER_BATCH_SIZE):
+            # Keras apply_valid_mask: the mean is over the positions that are not ignored
+            return per.sum() / kept.sum().clamp_min(1).to(per.dtype)
         return _reduce(per, self.reduction)
+
+    def valid_mask(self, y_true):
+        """Positions that count in the mean (None: all of them)."""
+        return None
 
     def get_config(self):
         return {"reduction": self.reduction, "name": self.name}
@@ -58,23 +69,52 @@ class Loss:
 class SparseCategoricalCrossentropy(Loss):
     name = "sparse_categorical_crossentropy"
 
-    def __init__(self, from_logits=False, reduction=Reduction.AUTO, name=None, label_smoothing=0.0):
+    def __init__(self, from_logits=False, reduction=Reduction.AUTO, name=None, label_smoothing=0.0,
+                 ignore_class=None):
+        """``y_pred [..., C]`` with ``y_true [...]``: ``[B, C]`` classifier outputs or the
+        ``[B, T, V]`` logits of a sequence model.  ``ignore_class``: positions whose label equals
+        it (padding tokens) have loss 0 and no gradient, and the ``AUTO`` /
+        ``SUM_OVER_BATCH_SIZE`` mean is over the other positions.  Under data parallelism that
+        mean is taken per replica and the replicas' means are then weighted by their sample
+        counts, as the loss already is: not by their numbers of valid positions."""
         super().__init__(reduction, name)
         self.from_logits = from_logits
         self.label_smoothing = label_smoothing
+        self.ignore_class = ignore_class
+
+    def valid_mask(self, y_true):
+        return None if self.ignore_class is None else y_true != self.ignore_class
 
     def per_example(self, y_true, y_pred):
+        C = y_pred.shape[-1]
         y = y_true.reshape(-1).long()
+        z = y_pred.float().reshape(-1, C)
+        kept = None
+        if self.ignore_class is not None:
+            kept = y != self.ignore_class
+            y = torch.where(kept, y, torch.zeros_like(y))
         if self.from_logits:
-            return F.cross_entropy(y_pred.float(), y, reduction="none", label_smoothing=self.label_smoothing)
-        p = y_pred.float().clamp_min(1e-7)
-        return F.nll_loss(torch.log(p / p.sum(-1, keepdim=True)), y, reduction="none")
+            per = F.cross_entropy(z, y, reduction="none", label_smoothing=self.label_smoothing)
+        else:
+            p = z.clamp_min(1e-7)
+            per = F.nll_loss(torch.log(p / p.sum(-1, keepdim=True)), y, reduction="none")
+        if kept is not None:
+            per = per * kept.to(per.dtype)
+        return per.reshape(y_pred.shape[:-1])
 
     def fused_logits_loss(self, logits, y_true, acc=None, acc_weight=1.0):
         """(mean loss, correct flags) via the fused softmax-xent kernel; ``acc`` (device fp32
         [3]) accumulates [loss sum, correct count, rows] for the metrics inside the kernel."""
+        if self.ignore_class is not None:
+            return ops.softmax_cross_entropy(logits, y_true.reshape(-1), label_smoothing=self.label_smoothing,
+                                             acc=acc, acc_weight=acc_weight, ignore_index=self.ignore_class,
+                                             denom="valid")
         return ops.softmax_cross_entropy(logits, y_true.reshape(-1), label_smoothing=self.label_smoothing, acc=acc,
                                          acc_weight=acc_weight)
+
+    def get_config(self):
+        return {**super().get_config(), "from_logits": self.from_logits, "label_smoothing": self.label_smoothing,
+                "ignore_class": self.ignore_class}
 
 
 class CategoricalCrossentropy(Loss):

@@ -334,9 +334,12 @@ class Model(Layer):
 
     def _metrics_fusable(self):
         """Loss and accuracy state kept by the fused loss kernel itself (device accumulator,
-        read once per log): fused sparse-xent with only sparse-categorical-accuracy metrics."""
-        return self._fused_xent and all(type(m) is metrics_mod.SparseCategoricalAccuracy
-                                        for m in self.compiled_metrics)
+        read once per log): fused sparse-xent with only sparse-categorical-accuracy metrics.
+        A sequence model's state counts positions (rows = B*T).  Not with an ``ignore_class``:
+        the kernel's correct count then leaves the ignored positions out, while the accuracy
+        stays Keras's, over all positions (``SparseCategoricalAccuracy.update_state``)."""
+        return (self._fused_xent and getattr(self.loss, "ignore_class", None) is None
+                and all(type(m) is metrics_mod.SparseCategoricalAccuracy for m in self.compiled_metrics))
 
     def train_step(self, xb, yb, sample_weight=None, loss_weight=1.0, n_real=None):
         """One replica step.  ``loss_weight`` rescales this replica's mean loss so that the

@@ -64,6 +64,11 @@ int ca_softmax_xent(const void*, int, const int64_t*, int, int, float, float, fl
 int ca_softmax_xent_batch(const void*, long, int, const int64_t*, int, int, float, float, float*, float*, void*, float*,
                           float,
                           hipStream_t);
+int ca_xent_vocab_resident_max(int);
+int ca_xent_vocab(const void*, long, int, const int64_t*, long, int, float, const float*, float, float*, float*, void*,
+                  hipStream_t);
+int ca_xent_vocab_count(const int64_t*, long, int, float*, hipStream_t);
+int ca_xent_vocab_finalize(const float*, const float*, long, float, const float*, float*, float*, float, hipStream_t);
 int ca_maxpool_fwd(const bf16_t*, bf16_t*, uint8_t*, int, int, int, int, int, int, int, int, int, hipStream_t);
 int ca_maxpool_bwd(const bf16_t*, const uint8_t*, bf16_t*, int, int, int, int, int, int, int, int, int, hipStream_t);
 int ca_gap_fwd(const bf16_t*, void*, int, int, int, int, hipStream_t);
@@ -340,6 +345,20 @@ PYBIND11_MODULE(_C, m) {
                                  u64 dz, u64 acc, float acc_w, u64 s) {
     check(ca_softmax_xent_batch(P(const void*, z), ldz, bf, P(const int64_t*, labels), B, C, gs, ls, P(float*, mean),
                                 P(float*, correct), P(void*, dz), P(float*, acc), acc_w, S(s)), "softmax_xent_batch");
+  });
+  m.def("xent_vocab_resident_max", [](int bf) { return ca_xent_vocab_resident_max(bf); });
+  m.def("xent_vocab", [](u64 z, long ldz, int bf, u64 labels, long N, int C, float scale, u64 scale_dev, float ls,
+                         u64 loss, u64 correct, u64 dz, u64 s) {
+    check(ca_xent_vocab(P(const void*, z), ldz, bf, P(const int64_t*, labels), N, C, scale, P(const float*, scale_dev),
+                        ls, P(float*, loss), P(float*, correct), P(void*, dz), S(s)), "xent_vocab");
+  });
+  m.def("xent_vocab_count", [](u64 labels, long N, int C, u64 out, u64 s) {
+    check(ca_xent_vocab_count(P(const int64_t*, labels), N, C, P(float*, out), S(s)), "xent_vocab_count");
+  });
+  m.def("xent_vocab_finalize", [](u64 loss, u64 correct, long N, float scale, u64 cnt, u64 out, u64 acc, float acc_w,
+                                  u64 s) {
+    check(ca_xent_vocab_finalize(P(const float*, loss), P(const float*, correct), N, scale, P(const float*, cnt),
+                                 P(float*, out), P(float*, acc), acc_w, S(s)), "xent_vocab_finalize");
   });
   m.def("maxpool_fwd", [](u64 x, u64 y, u64 idx, int N, int H, int W, int C, int OH, int OW, int k, int st, int p,
                           u64 s) {
