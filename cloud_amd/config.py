@@ -63,7 +63,7 @@ _VARS = [
         "docs/performance.md: not slower from 1010 on (1024 x 1010: 0.98, 65536 x 1010: 0.78 of the row kernel's time)",
         "ops"),
     Var("CLOUD_AMD_GEMM", str, "native", "dense GEMMs: 'native' or 'torch'", "ops"),
-    Var("CLOUD_AMD_CONV", str, "native", "convolutions: 'native' or 'torch'", "ops"),
+    Var("CLOUD_AMD_CONV", str, "native", "convolutions, dense and depthwise: 'native' or 'torch'", "ops"),
     Var("CLOUD_AMD_GEMM_CORE", str, "auto", "GEMM core: 'auto' (128x128 LDS-DMA core plus the 256x256 two-phase "
         "core of ca_gemm256p8.h for large GEMMs), 'glds' (128 core only), 'vp8' (the two-phase 256 core whenever "
         "M, N >= 256), 'reg' (register staging); any other name selects 'auto'", "ops"),

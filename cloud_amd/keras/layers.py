@@ -148,6 +148,149 @@ class Conv2D(_Regularized, Layer):
         return c
 
 
+def _same_pads(size, kernel, strides, dilation=(1, 1)):
+    """TF's SAME split per axis ((top, bottom), (left, right)): ``Conv2D._same_pads``' formula on
+    the dilated kernel extent; the odd row / column goes to the bottom / right."""
+    out = []
+    for n, k, s, d in zip(size, kernel, strides, dilation):
+        k = (k - 1) * d + 1
+        tot = max((math.ceil(n / s) - 1) * s + k - n, 0)
+        out.append((tot // 2, tot - tot // 2))
+    return out
+
+
+def _init_name(init):
+    return init if isinstance(init, str) else "glorot_uniform"
+
+
+class DepthwiseConv2D(Layer):
+    """``tf.keras.layers.DepthwiseConv2D``: ``depthwise_kernel [kh, kw, cin, dm]`` (the Keras
+    layout; output channel ``c * dm + m`` reads input channel ``c``) and ``bias [cin * dm]``.
+    Under the mixed policy it runs ``ops.depthwise_conv2d`` natively, with bias and a fusable
+    activation in the kernel's epilogue and SAME padding passed as pads (no padded copy);
+    ``dilation_rate != 1`` is the same expression in PyTorch."""
+
+    def __init__(self, kernel_size, strides=(1, 1), padding="valid", depth_multiplier=1, data_format=None,
+                 dilation_rate=(1, 1), activation=None, use_bias=True, depthwise_initializer="glorot_uniform",
+                 bias_initializer="zeros", depthwise_regularizer=None, bias_regularizer=None, **kw):
+        super().__init__(**kw)
+        if data_format not in (None, "channels_last"):
+            raise ValueError("cloud_amd layers are channels_last (NHWC) only")
+        self.kernel_size = _pair(kernel_size)
+        self.strides = _pair(strides)
+        self.padding = padding.lower()
+        if self.padding not in ("valid", "same"):
+            raise ValueError(f"padding must be 'valid' or 'same', got {padding!r}")
+        self.depth_multiplier = int(depth_multiplier)
+        self.dilation_rate = _pair(dilation_rate)
+        self.activation = activations.get(activation)
+        self.use_bias = use_bias
+        self.depthwise_initializer, self.bias_initializer = depthwise_initializer, bias_initializer
+        self.depthwise_regularizer = regularizers.get(depthwise_regularizer)
+        self.bias_regularizer = regularizers.get(bias_regularizer)
+
+    def _new_depthwise_kernel(self, cin):
+        # drawn as [dm, kh, kw, cin], whose fans are Keras's for [kh, kw, cin, dm]:
+        # fan_in = kh*kw*cin, fan_out = kh*kw*dm
+        kh, kw = self.kernel_size
+        w = torch.empty(self.depth_multiplier, kh, kw, cin)
+        initializers.get(self.depthwise_initializer)(w)
+        return torch.nn.Parameter(w.permute(1, 2, 3, 0).contiguous().to(self.compute_dtype))
+
+    def build(self, input_shape):
+        cin = int(input_shape[-1])
+        self.depthwise_kernel = self._new_depthwise_kernel(cin)
+        if self.use_bias:
+            b = torch.empty(cin * self.depth_multiplier)
+            initializers.get(self.bias_initializer)(b)
+            self.bias = torch.nn.Parameter(b.to(_bias_dtype(self)))
+        else:
+            self.bias = None
+
+    def _depthwise(self, x, bias, act):
+        x = x.to(self.depthwise_kernel.dtype)
+        pads = ((0, 0), (0, 0))
+        if self.padding == "same":
+            pads = _same_pads(x.shape[1:3], self.kernel_size, self.strides, self.dilation_rate)
+        return ops.depthwise_conv2d(x.contiguous(), self.depthwise_kernel, bias, self.strides, pads, act,
+                                    dilation=self.dilation_rate)
+
+    def call(self, x, training=None):
+        act, rest = _fused_act(self.activation)
+        y = self._depthwise(x, self.bias, act)
+        return rest(y) if rest is not None else y
+
+    def _penalties(self):
+        return ((self.depthwise_regularizer, self.depthwise_kernel), (self.bias_regularizer, self.bias))
+
+    def regularization_loss(self):
+        out = None
+        for reg, w in self._penalties():
+            if reg is not None and w is not None and self.trainable:
+                p = reg(w)
+                out = p if out is None else out + p
+        return out if out is not None else 0.0
+
+    def get_config(self):
+        c = super().get_config()
+        c.update(kernel_size=list(self.kernel_size), strides=list(self.strides), padding=self.padding,
+                 depth_multiplier=self.depth_multiplier, dilation_rate=list(self.dilation_rate),
+                 activation=activations.serialize(self.activation), use_bias=self.use_bias,
+                 depthwise_initializer=_init_name(self.depthwise_initializer),
+                 bias_initializer=_init_name(self.bias_initializer),
+                 depthwise_regularizer=regularizers.serialize(self.depthwise_regularizer),
+                 bias_regularizer=regularizers.serialize(self.bias_regularizer))
+        return c
+
+
+class SeparableConv2D(DepthwiseConv2D):
+    """``tf.keras.layers.SeparableConv2D``: the depthwise convolution (no bias, no activation)
+    followed by the 1x1 pointwise convolution ``pointwise_kernel [filters, 1, 1, cin * dm]`` on
+    the in-tree GEMM, bias and activation in its epilogue.  Weight order: ``depthwise_kernel,
+    pointwise_kernel, bias``."""
+
+    def __init__(self, filters, kernel_size, strides=(1, 1), padding="valid", data_format=None,
+                 dilation_rate=(1, 1), depth_multiplier=1, activation=None, use_bias=True,
+                 depthwise_initializer="glorot_uniform", pointwise_initializer="glorot_uniform",
+                 bias_initializer="zeros", depthwise_regularizer=None, pointwise_regularizer=None,
+                 bias_regularizer=None, **kw):
+        super().__init__(kernel_size, strides=strides, padding=padding, depth_multiplier=depth_multiplier,
+                         data_format=data_format, dilation_rate=dilation_rate, activation=activation,
+                         use_bias=use_bias, depthwise_initializer=depthwise_initializer,
+                         bias_initializer=bias_initializer, depthwise_regularizer=depthwise_regularizer,
+                         bias_regularizer=bias_regularizer, **kw)
+        self.filters = int(filters)
+        self.pointwise_initializer = pointwise_initializer
+        self.pointwise_regularizer = regularizers.get(pointwise_regularizer)
+
+    def build(self, input_shape):
+        cin = int(input_shape[-1])
+        self.depthwise_kernel = self._new_depthwise_kernel(cin)
+        w = torch.empty(self.filters, 1, 1, cin * self.depth_multiplier)
+        initializers.get(self.pointwise_initializer)(w)
+        self.pointwise_kernel = torch.nn.Parameter(w.to(self.compute_dtype))
+        if self.use_bias:
+            b = torch.empty(self.filters)
+            initializers.get(self.bias_initializer)(b)
+            self.bias = torch.nn.Parameter(b.to(_bias_dtype(self)))
+        else:
+            self.bias = None
+
+    def call(self, x, training=None):
+        act, rest = _fused_act(self.activation)
+        y = conv_act_op(self._depthwise(x, None, None), self.pointwise_kernel, self.bias, 1, 0, act)
+        return rest(y) if rest is not None else y
+
+    def _penalties(self):
+        return super()._penalties() + ((self.pointwise_regularizer, self.pointwise_kernel),)
+
+    def get_config(self):
+        c = super().get_config()
+        c.update(filters=self.filters, pointwise_initializer=_init_name(self.pointwise_initializer),
+                 pointwise_regularizer=regularizers.serialize(self.pointwise_regularizer))
+        return c
+
+
 class _Pool2D(Layer):
     def __init__(self, pool_size=(2, 2), strides=None, padding="valid", **kw):
         super().__init__(**kw)
@@ -742,7 +885,8 @@ class TorchModule(Layer):
 
 
 LAYERS = {cls.__name__: cls for cls in [
-    Dense, Conv2D, MaxPooling2D, AveragePooling2D, GlobalAveragePooling2D, GlobalMaxPooling2D, Flatten, Reshape,
+    Dense, Conv2D, DepthwiseConv2D, SeparableConv2D, MaxPooling2D, AveragePooling2D, GlobalAveragePooling2D,
+    GlobalMaxPooling2D, Flatten, Reshape,
     Dropout, Activation, ReLU, Softmax, BatchNormalization, LayerNormalization, Embedding, Rescaling, Add,
     Concatenate, MultiHeadAttention, RandomFlip, RandomRotation, RandomTranslation, RandomZoom, RandomContrast,
     InputLayer]}
@@ -751,6 +895,7 @@ AvgPool2D = AveragePooling2D
 GlobalAvgPool2D = GlobalAveragePooling2D
 GlobalMaxPool2D = GlobalMaxPooling2D
 Convolution2D = Conv2D
+SeparableConvolution2D = SeparableConv2D
 
 
 class experimental:  # namespace parity: tf.keras.layers.experimental.preprocessing (TF 2.3)

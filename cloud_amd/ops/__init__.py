@@ -8,6 +8,7 @@ from ._ext import load as load_extension, ops_mode, use_native  # noqa: F401
 from .attention import attention, cross_attention  # noqa: F401
 from .batchnorm import bn_act  # noqa: F401
 from .conv import conv2d_nhwc  # noqa: F401
+from .depthwise import depthwise_conv2d  # noqa: F401
 from .gemm import linear  # noqa: F401
 from .infer import conv_bn_act_infer  # noqa: F401
 from .layernorm import layer_norm  # noqa: F401

@@ -252,6 +252,84 @@ def conv_wgrad(dy, x, w_shape, stride, padding, out, beta=1.0, blocks=None):
     return out
 
 
+# ------------------------------------------------------- depthwise convolution
+# activation codes of the depthwise forward epilogue (those of ops/dense.py ACT)
+DW_ACT = {None: 0, "linear": 0, "gelu": 1, "relu": 2, "tanh": 3, "elu": 5}
+
+
+def _dw_check(name, acts, w, stride, pads):
+    for t in acts:
+        if t is not None and (t.dtype != torch.bfloat16 or t.dim() != 4 or not t.is_contiguous() or not t.is_cuda):
+            raise ValueError(f"{name}: contiguous NHWC bf16 CUDA tensors expected")
+    KH, KW = int(w[0]), int(w[1])
+    if not (1 <= KH <= 7 and 1 <= KW <= 7 and 1 <= stride[0] <= 4 and 1 <= stride[1] <= 4):
+        raise ValueError(f"{name}: kernel sizes 1..7 and strides 1..4 are supported, got {KH}x{KW} / {stride}")
+    if pads[0] < 0 or pads[1] < 0:
+        raise ValueError(f"{name}: negative padding")
+
+
+def dwconv_fwd(x, w, stride, pads, out_hw_, bias=None, act=None, out=None, pre=None):
+    """y = act(dwconv(x, w) + bias) (csrc/kernels/dwconv.hip).  x [N, H, W, Cin] bf16, w
+    [KH, KW, Cin, DM] bf16, bias fp32 [Cin*DM] or None; ``stride`` = (sh, sw), ``pads`` =
+    (top, left) -- rows / columns past the bottom / right edge read as zero -- and ``out_hw_``
+    = (OH, OW).  ``pre``: optional bf16 tensor of y's shape that receives the pre-activation."""
+    ext = _ext.load(required=True)
+    N, H, W, Cin = x.shape
+    KH, KW, Cw, DM = w.shape
+    OH, OW = out_hw_
+    Cout = Cin * DM
+    y = out if out is not None else torch.empty((N, OH, OW, Cout), dtype=torch.bfloat16, device=x.device)
+    _dw_check("dwconv_fwd", (x, y, pre), w.shape, stride, pads)
+    if (Cw != Cin or w.dtype != torch.bfloat16 or not w.is_contiguous() or tuple(y.shape) != (N, OH, OW, Cout)
+            or (pre is not None and pre.shape != y.shape)):
+        raise ValueError("dwconv_fwd: w [KH, KW, Cin, DM] bf16 contiguous and y / pre [N, OH, OW, Cin*DM] expected")
+    if bias is not None and (bias.dtype != torch.float32 or bias.numel() != Cout or not bias.is_contiguous()):
+        raise ValueError("dwconv_fwd: bias must be a contiguous fp32 [Cin*DM] vector")
+    ext.dwconv_fwd(x.data_ptr(), w.data_ptr(), _ext.ptr(bias), y.data_ptr(), _ext.ptr(pre), N, H, W, Cin, DM, KH, KW,
+                   stride[0], stride[1], pads[0], pads[1], OH, OW, DW_ACT[act], _st(x.device))
+    _log("dwfwd%dx%d" % (KH, KW), N * OH * OW, Cout, KH * KW, _nb(x, w, y, pre))
+    return y
+
+
+def dwconv_dgrad(dy, w, x_shape, stride, pads, out=None):
+    """dx [N, H, W, Cin] bf16 of :func:`dwconv_fwd` from dy [N, OH, OW, Cin*DM] (gather form:
+    every dx element is written once; pixels that no output reads get exactly 0)."""
+    ext = _ext.load(required=True)
+    N, H, W, Cin = x_shape
+    KH, KW, Cw, DM = w.shape
+    dx = out if out is not None else torch.empty((N, H, W, Cin), dtype=torch.bfloat16, device=dy.device)
+    _dw_check("dwconv_dgrad", (dy, dx), w.shape, stride, pads)
+    if (Cw != Cin or w.dtype != torch.bfloat16 or not w.is_contiguous() or dy.shape[0] != N
+            or dy.shape[3] != Cin * DM or tuple(dx.shape) != (N, H, W, Cin)):
+        raise ValueError("dwconv_dgrad: w [KH, KW, Cin, DM] bf16 contiguous, dy [N, OH, OW, Cin*DM], dx [N, H, W, Cin]")
+    ext.dwconv_dgrad(dy.data_ptr(), w.data_ptr(), dx.data_ptr(), N, H, W, Cin, DM, KH, KW, stride[0], stride[1],
+                     pads[0], pads[1], dy.shape[1], dy.shape[2], _st(dy.device))
+    _log("dwdgrad%dx%d" % (KH, KW), N * H * W, Cin, KH * KW * DM, _nb(dy, w, dx))
+    return dx
+
+
+def dwconv_wgrad(dy, x, w_shape, stride, pads, out=None, accumulate=False):
+    """dw [KH, KW, Cin, DM] fp32 of :func:`dwconv_fwd`: ``out`` is overwritten, or added to with
+    ``accumulate``.  Two launches (per-chunk partials, then a fixed-order sum): bitwise
+    reproducible.  The partials workspace comes from the caching allocator."""
+    ext = _ext.load(required=True)
+    N, H, W, Cin = x.shape
+    KH, KW, Cw, DM = w_shape
+    dw = out if out is not None else torch.empty(tuple(w_shape), dtype=torch.float32, device=x.device)
+    _dw_check("dwconv_wgrad", (dy, x), w_shape, stride, pads)
+    if (Cw != Cin or dy.shape[0] != N or dy.shape[3] != Cin * DM or dw.dtype != torch.float32
+            or not dw.is_contiguous() or tuple(dw.shape) != tuple(w_shape) or (out is None and accumulate)):
+        raise ValueError("dwconv_wgrad: dy [N, OH, OW, Cin*DM], x [N, H, W, Cin] and a contiguous fp32 out "
+                         "[KH, KW, Cin, DM] expected")
+    OH, OW = dy.shape[1], dy.shape[2]
+    chunks = ext.dwconv_wgrad_chunks(N, OH, OW)
+    ws = torch.empty(chunks * KH * KW * Cin * DM, dtype=torch.float32, device=x.device)
+    ext.dwconv_wgrad(dy.data_ptr(), x.data_ptr(), dw.data_ptr(), int(bool(accumulate)), ws.data_ptr(), N, H, W, Cin,
+                     DM, KH, KW, stride[0], stride[1], pads[0], pads[1], OH, OW, _st(x.device))
+    _log("dwwgrad%dx%d" % (KH, KW), KH * KW, Cin * DM, N * OH * OW, _nb(dy, x, dw) + 2 * _nb(ws))
+    return dw
+
+
 # ------------------------------------------- BN folded into the consuming 1x1 GEMM
 XA_BN_RELU, XA_BN_RES_RELU, XA_BN_BWD, XA_BN_RESBN_RELU = 0, 1, 2, 3
 

@@ -141,6 +141,13 @@ int ca_attn_cross_fwd(const bf16_t*, const bf16_t*, bf16_t*, float*, const int*,
 int ca_attn_cross_bwd(const bf16_t*, const bf16_t*, const bf16_t*, const bf16_t*, const float*, float*, bf16_t*,
                       bf16_t*, const int*, const uint8_t*, long, long, long, int, int, int, int, int, long, long, float,
                       float, uint64_t, hipStream_t);
+int ca_dwconv_fwd(const bf16_t*, const bf16_t*, const float*, bf16_t*, bf16_t*, int, int, int, int, int, int, int, int,
+                  int, int, int, int, int, int, hipStream_t);
+int ca_dwconv_dgrad(const bf16_t*, const bf16_t*, bf16_t*, int, int, int, int, int, int, int, int, int, int, int, int,
+                    int, hipStream_t);
+long ca_dwconv_wgrad_chunks(int, int, int);
+int ca_dwconv_wgrad(const bf16_t*, const bf16_t*, float*, int, float*, int, int, int, int, int, int, int, int, int,
+                    int, int, int, int, hipStream_t);
 }
 
 #define P(T, x) reinterpret_cast<T>(static_cast<uintptr_t>(x))
@@ -573,5 +580,22 @@ PYBIND11_MODULE(_C, m) {
                             P(const int*, klen), P(const uint8_t*, mask), msb, msh, mst, B, T, S_, H, D, ldq, ldkv,
                             scale, p, seed, S(s)),
           "attn_cross_bwd");
+  });
+  // depthwise convolution (dwconv.hip): weight [KH, KW, Cin, DM], top / left pads, OH / OW given
+  m.def("dwconv_fwd", [](u64 x, u64 w, u64 bias, u64 y, u64 pre, int Nb, int H, int W, int Cin, int DM, int KH, int KW,
+                         int sh, int sw, int pt, int pl, int OH, int OW, int act, u64 s) {
+    check(ca_dwconv_fwd(P(const bf16_t*, x), P(const bf16_t*, w), P(const float*, bias), P(bf16_t*, y),
+                        P(bf16_t*, pre), Nb, H, W, Cin, DM, KH, KW, sh, sw, pt, pl, OH, OW, act, S(s)), "dwconv_fwd");
+  });
+  m.def("dwconv_dgrad", [](u64 dy, u64 w, u64 dx, int Nb, int H, int W, int Cin, int DM, int KH, int KW, int sh,
+                           int sw, int pt, int pl, int OH, int OW, u64 s) {
+    check(ca_dwconv_dgrad(P(const bf16_t*, dy), P(const bf16_t*, w), P(bf16_t*, dx), Nb, H, W, Cin, DM, KH, KW, sh, sw,
+                          pt, pl, OH, OW, S(s)), "dwconv_dgrad");
+  });
+  m.def("dwconv_wgrad_chunks", [](int Nb, int OH, int OW) { return ca_dwconv_wgrad_chunks(Nb, OH, OW); });
+  m.def("dwconv_wgrad", [](u64 dy, u64 x, u64 dw, int accumulate, u64 ws, int Nb, int H, int W, int Cin, int DM,
+                           int KH, int KW, int sh, int sw, int pt, int pl, int OH, int OW, u64 s) {
+    check(ca_dwconv_wgrad(P(const bf16_t*, dy), P(const bf16_t*, x), P(float*, dw), accumulate, P(float*, ws), Nb, H,
+                          W, Cin, DM, KH, KW, sh, sw, pt, pl, OH, OW, S(s)), "dwconv_wgrad");
   });
 }
