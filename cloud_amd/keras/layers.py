@@ -291,12 +291,40 @@ class SeparableConv2D(DepthwiseConv2D):
         return c
 
 
+def _pool_nhwc(op, x, pool_size, strides, padding):
+    """``op`` (an ``ops.*_pool2d_nhwc``) under TF's "valid" / "same" geometry.  "same" goes to the op
+    as its pad split plus the output size, so no padded copy is made; where it pads nothing it is
+    "valid"."""
+    x = x.contiguous()
+    if padding == "same":
+        pads = _same_pads(x.shape[1:3], pool_size, strides)
+        if any(p for ax in pads for p in ax):
+            out_hw = (math.ceil(x.shape[1] / strides[0]), math.ceil(x.shape[2] / strides[1]))
+            return op(x, pool_size, strides, pads, out_hw)
+    return op(x, pool_size, strides, 0)
+
+
+def _check_padding(padding):
+    padding = padding.lower()
+    if padding not in ("valid", "same"):
+        raise ValueError(f"padding must be 'valid' or 'same', got {padding!r}")
+    return padding
+
+
 class _Pool2D(Layer):
+    """``pool_size`` and ``strides`` are ints or (h, w) pairs, ``padding`` "valid" or "same" (TF's
+    split: the odd row / column goes to the bottom / right).  [N, H, W, C] -> [N, OH, OW, C]."""
+
+    _op = None
+
     def __init__(self, pool_size=(2, 2), strides=None, padding="valid", **kw):
         super().__init__(**kw)
         self.pool_size = _pair(pool_size)
         self.strides = _pair(strides) if strides is not None else self.pool_size
-        self.padding = padding.lower()
+        self.padding = _check_padding(padding)
+
+    def call(self, x, training=None):
+        return _pool_nhwc(type(self)._op, x, self.pool_size, self.strides, self.padding)
 
     def get_config(self):
         c = super().get_config()
@@ -305,21 +333,48 @@ class _Pool2D(Layer):
 
 
 class MaxPooling2D(_Pool2D):
-    def call(self, x, training=None):
-        k, s = self.pool_size[0], self.strides[0]
-        if self.padding == "same":
-            H, W = x.shape[1], x.shape[2]
-            ph = max((math.ceil(H / s) - 1) * s + k - H, 0)
-            pw = max((math.ceil(W / s) - 1) * s + k - W, 0)
-            if ph or pw:
-                x = F.pad(x, (0, 0, pw // 2, pw - pw // 2, ph // 2, ph - ph // 2), value=float("-inf"))
-        return ops.max_pool2d_nhwc(x.contiguous(), k, s, 0)
+    _op = staticmethod(ops.max_pool2d_nhwc)
 
 
 class AveragePooling2D(_Pool2D):
+    """The divisor is the number of in-image taps: "same" padding is not averaged in (TF)."""
+
+    _op = staticmethod(ops.avg_pool2d_nhwc)
+
+
+def _one(v):
+    return int(v) if isinstance(v, int) else int(tuple(v)[0])
+
+
+class _Pool1D(Layer):
+    """``tf.keras.layers.{Max,Average}Pooling1D``: [B, T, C] -> [B, OT, C] over the steps, through
+    the 2D ops on the [B, 1, T, C] view (no copy)."""
+
+    _op = None
+
+    def __init__(self, pool_size=2, strides=None, padding="valid", **kw):
+        super().__init__(**kw)
+        self.pool_size = _one(pool_size)
+        self.strides = _one(strides) if strides is not None else self.pool_size
+        self.padding = _check_padding(padding)
+
     def call(self, x, training=None):
-        y = F.avg_pool2d(x.permute(0, 3, 1, 2), self.pool_size, self.strides)
-        return y.permute(0, 2, 3, 1).contiguous()
+        y = _pool_nhwc(type(self)._op, x.contiguous().unsqueeze(1), (1, self.pool_size), (1, self.strides),
+                       self.padding)
+        return y.squeeze(1)
+
+    def get_config(self):
+        c = super().get_config()
+        c.update(pool_size=[self.pool_size], strides=[self.strides], padding=self.padding)
+        return c
+
+
+class MaxPooling1D(_Pool1D):
+    _op = staticmethod(ops.max_pool2d_nhwc)
+
+
+class AveragePooling1D(_Pool1D):
+    _op = staticmethod(ops.avg_pool2d_nhwc)
 
 
 class GlobalAveragePooling2D(Layer):
@@ -330,6 +385,27 @@ class GlobalAveragePooling2D(Layer):
 class GlobalMaxPooling2D(Layer):
     def call(self, x, training=None):
         return ops.global_max_pool_nhwc(x.contiguous())
+
+
+def _no_mask(layer, mask):
+    if mask is not None:
+        raise ValueError(f"{type(layer).__name__}: a mask is not supported")
+
+
+class GlobalAveragePooling1D(Layer):
+    """[B, T, C] -> [B, C], the mean over the steps (the [B, 1, T, C] view through the 2D op)."""
+
+    def call(self, x, training=None, mask=None):
+        _no_mask(self, mask)
+        return ops.global_avg_pool_nhwc(x.contiguous().unsqueeze(1))
+
+
+class GlobalMaxPooling1D(Layer):
+    """[B, T, C] -> [B, C], the maximum over the steps."""
+
+    def call(self, x, training=None, mask=None):
+        _no_mask(self, mask)
+        return ops.global_max_pool_nhwc(x.contiguous().unsqueeze(1))
 
 
 class Flatten(Layer):
@@ -886,7 +962,7 @@ class TorchModule(Layer):
 
 LAYERS = {cls.__name__: cls for cls in [
     Dense, Conv2D, DepthwiseConv2D, SeparableConv2D, MaxPooling2D, AveragePooling2D, GlobalAveragePooling2D,
-    GlobalMaxPooling2D, Flatten, Reshape,
+    GlobalMaxPooling2D, MaxPooling1D, AveragePooling1D, GlobalAveragePooling1D, GlobalMaxPooling1D, Flatten, Reshape,
     Dropout, Activation, ReLU, Softmax, BatchNormalization, LayerNormalization, Embedding, Rescaling, Add,
     Concatenate, MultiHeadAttention, RandomFlip, RandomRotation, RandomTranslation, RandomZoom, RandomContrast,
     InputLayer]}
@@ -894,6 +970,10 @@ MaxPool2D = MaxPooling2D
 AvgPool2D = AveragePooling2D
 GlobalAvgPool2D = GlobalAveragePooling2D
 GlobalMaxPool2D = GlobalMaxPooling2D
+MaxPool1D = MaxPooling1D
+AvgPool1D = AveragePooling1D
+GlobalAvgPool1D = GlobalAveragePooling1D
+GlobalMaxPool1D = GlobalMaxPooling1D
 Convolution2D = Conv2D
 SeparableConvolution2D = SeparableConv2D
 

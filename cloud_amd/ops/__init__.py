@@ -13,5 +13,5 @@ from .gemm import linear  # noqa: F401
 from .infer import conv_bn_act_infer  # noqa: F401
 from .layernorm import layer_norm  # noqa: F401
 from .losses import backward_with_seed, softmax_cross_entropy, unit_seed  # noqa: F401
-from .pooling import global_avg_pool_nhwc, global_max_pool_nhwc, max_pool2d_nhwc  # noqa: F401
+from .pooling import avg_pool2d_nhwc, global_avg_pool_nhwc, global_max_pool_nhwc, max_pool2d_nhwc  # noqa: F401
 from .dropout import dropout  # noqa: F401

@@ -1,7 +1,9 @@
-"""NHWC pooling ops (K7): MaxPool2D and global average pooling.
+"""NHWC pooling ops (K7): max / average pooling at any window and the global pools.
 
-HIP path: ``csrc/kernels/pool.hip``.  CPU / torch-mode path: PyTorch NCHW ops on
-permuted views.  Parity: Keras ``MaxPooling2D`` / ``GlobalAveragePooling2D``
+HIP path: ``csrc/kernels/pool.hip`` (square symmetric max pool with ``C % 8 == 0``, global
+pools, the fused ResNet stem tail) and ``csrc/kernels/pool2d.hip`` (max / average at any
+window, stride, asymmetric pads and channel count).  CPU / torch-mode path: PyTorch NCHW ops on
+permuted views.  Parity: Keras ``MaxPooling2D`` / ``AveragePooling2D`` / ``GlobalAveragePooling2D``
 (reference ``core/tests/testdata/mnist_example_using_fit.py:58``,
 ``core/tests/examples/call_run_within_script_with_keras_fit.py:83``).
 """
@@ -11,7 +13,9 @@ import torch
 import torch.nn.functional as F
 
 from .. import config
-from . import _ext
+from . import _ext, raw
+from .dense import _pair2
+from .depthwise import _pads
 
 
 def _out(n, k, s, p):
@@ -45,12 +49,101 @@ class _MaxPoolFn(torch.autograd.Function):
         return dx, None, None, None
 
 
-def max_pool2d_nhwc(x, kernel_size, stride=None, padding=0):
-    stride = kernel_size if stride is None else stride
-    if x.dtype == torch.bfloat16 and x.shape[-1] % 8 == 0 and _ext.use_native(x):
-        return _MaxPoolFn.apply(x, kernel_size, stride, padding)
-    y = F.max_pool2d(x.permute(0, 3, 1, 2), kernel_size, stride, padding)
+class _MaxPool2dFn(torch.autograd.Function):
+    """Max pool at any window on ``pool2d.hip``: the argmax bytes are the only saved state."""
+
+    @staticmethod
+    def forward(ctx, x, k, s, pads, out_hw):
+        y, idx = raw.pool2d_max_fwd(x, k, s, pads, out_hw)
+        ctx.save_for_backward(idx)
+        ctx.cfg = (tuple(x.shape), k, s, pads)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (idx,) = ctx.saved_tensors
+        x_shape, k, s, pads = ctx.cfg
+        return raw.pool2d_max_bwd(dy.contiguous(), idx, x_shape, k, s, pads), None, None, None, None
+
+
+class _AvgPool2dFn(torch.autograd.Function):
+    """Average pool at any window on ``pool2d.hip`` (divisor: the in-image taps); nothing saved."""
+
+    @staticmethod
+    def forward(ctx, x, k, s, pads, out_hw):
+        ctx.cfg = (tuple(x.shape), k, s, pads)
+        return raw.pool2d_avg_fwd(x, k, s, pads, out_hw)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x_shape, k, s, pads = ctx.cfg
+        return raw.pool2d_avg_bwd(dy.contiguous(), x_shape, k, s, pads), None, None, None, None
+
+
+def _geometry(x, kernel_size, stride, padding, out_hw):
+    """(kernel, stride, ((top, bottom), (left, right)), (OH, OW)) from the ops' argument forms;
+    with ``out_hw`` the bottom / right pads are what that output size reads (negative: rows /
+    columns the windows never reach)."""
+    k = _pair2(kernel_size)
+    s = k if stride is None else _pair2(stride)
+    (pt, pb), (pl, pr) = _pads(padding)
+    H, W = x.shape[1], x.shape[2]
+    if out_hw is None:
+        out_hw = ((H + pt + pb - k[0]) // s[0] + 1, (W + pl + pr - k[1]) // s[1] + 1)
+    else:
+        out_hw = (int(out_hw[0]), int(out_hw[1]))
+        pb = (out_hw[0] - 1) * s[0] + k[0] - H - pt
+        pr = (out_hw[1] - 1) * s[1] + k[1] - W - pl
+    return k, s, ((pt, pb), (pl, pr)), out_hw
+
+
+def _pool2d_native(x, k, s, pads, out_hw):
+    """The calls that run on ``pool2d.hip``: CUDA bf16 NHWC, a geometry its launchers accept."""
+    return (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4 and x.shape[0] > 0 and x.numel() < 2 ** 31
+            and raw.pool2d_geom_ok(x.shape, k, s, (pads[0][0], pads[1][0]), out_hw) and _ext.use_native(x))
+
+
+def max_pool2d_nhwc(x, kernel_size, stride=None, padding=0, out_hw=None):
+    """Max pool of x [N, H, W, C] -> [N, OH, OW, C].  ``kernel_size`` and ``stride`` are ints or
+    (h, w) pairs (``stride`` defaults to the window); ``padding`` an int, an (h, w) pair or
+    ((top, bottom), (left, right)); padded taps never win.  ``out_hw`` = (OH, OW) overrides the
+    output size the pads imply (taps past the bottom / right edge are skipped).
+
+    A square window with one stride, one symmetric pad, no ``out_hw`` and ``C % 8 == 0`` runs on
+    the kernels of ``pool.hip`` (the ResNet route); every other CUDA bf16 call whose windows all
+    hold an in-image tap runs on ``pool2d.hip``; anything else is the same expression in PyTorch."""
+    k, s, pads, ohw = _geometry(x, kernel_size, stride, padding, out_hw)
+    (pt, pb), (pl, pr) = pads
+    square = out_hw is None and k[0] == k[1] and s[0] == s[1] and pt == pb == pl == pr  # (k, s, p) says it all
+    if square and x.dtype == torch.bfloat16 and x.shape[-1] % 8 == 0 and _ext.use_native(x):
+        return _MaxPoolFn.apply(x, k[0], s[0], pt)
+    if _pool2d_native(x, k, s, pads, ohw):
+        return _MaxPool2dFn.apply(x.contiguous(), k, s, (pt, pl), ohw)
+    xc = x.permute(0, 3, 1, 2)
+    if square:
+        y = F.max_pool2d(xc, k[0], s[0], pt)
+    else:
+        y = F.max_pool2d(F.pad(xc, (pl, pr, pt, pb), value=float("-inf")), k, s)
     return y.permute(0, 2, 3, 1).contiguous()
+
+
+def avg_pool2d_nhwc(x, kernel_size, stride=None, padding=0, out_hw=None):
+    """Average pool of x [N, H, W, C] -> [N, OH, OW, C] over the in-image taps of each window:
+    padding is excluded from the divisor (TF's ``AveragePooling2D``).  Arguments as
+    :func:`max_pool2d_nhwc`.  CUDA bf16 calls whose windows all hold an in-image tap run on
+    ``pool2d.hip``; anything else is the same expression in PyTorch: the window sums of the
+    zero-padded input over the window sums of a padded map of ones (fp32 sums for 16-bit inputs)."""
+    k, s, pads, ohw = _geometry(x, kernel_size, stride, padding, out_hw)
+    if _pool2d_native(x, k, s, pads, ohw):
+        return _AvgPool2dFn.apply(x.contiguous(), k, s, (pads[0][0], pads[1][0]), ohw)
+    (pt, pb), (pl, pr) = pads
+    xc = x.permute(0, 3, 1, 2)
+    wide = xc.float() if x.dtype in (torch.bfloat16, torch.float16) else xc
+    ones = torch.ones((1, 1, x.shape[1], x.shape[2]), dtype=wide.dtype, device=x.device)
+    total = F.avg_pool2d(F.pad(wide, (pl, pr, pt, pb)), k, s, divisor_override=1)
+    count = F.avg_pool2d(F.pad(ones, (pl, pr, pt, pb)), k, s, divisor_override=1)
+    y = total / count.clamp_(min=1)  # a window wholly in the padding: 0
+    return y.to(x.dtype).permute(0, 2, 3, 1).contiguous()
 
 
 class _GapFn(torch.autograd.Function):

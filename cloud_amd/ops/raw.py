@@ -330,6 +330,101 @@ def dwconv_wgrad(dy, x, w_shape, stride, pads, out=None, accumulate=False):
     return dw
 
 
+# ------------------------------------------------- pooling at any window (pool2d.hip)
+def pool2d_geom_ok(x_shape, kernel, stride, pads, out_hw_):
+    """What the pool2d launchers accept (they check it again before launching): a window of at
+    most 255 taps (the argmax byte), top / left pads smaller than the window, and a last window
+    that starts inside the image, so every window holds at least one in-image tap."""
+    N, H, W, C = x_shape
+    (KH, KW), (sh, sw), (pt, pl), (OH, OW) = kernel, stride, pads, out_hw_
+    return (N >= 1 and H >= 1 and W >= 1 and C >= 1 and KH >= 1 and KW >= 1 and KH * KW <= 255 and sh >= 1
+            and sw >= 1 and 0 <= pt < KH and 0 <= pl < KW and OH >= 1 and OW >= 1
+            and (OH - 1) * sh - pt <= H - 1 and (OW - 1) * sw - pl <= W - 1
+            and N * H * W * C < 2 ** 31 and N * OH * OW * C < 2 ** 31)
+
+
+def _pool_check(name, acts, x_shape, kernel, stride, pads, out_hw_):
+    for t in acts:
+        if t.dtype != torch.bfloat16 or t.dim() != 4 or not t.is_contiguous() or not t.is_cuda:
+            raise ValueError(f"{name}: contiguous NHWC bf16 CUDA tensors expected")
+    if not pool2d_geom_ok(x_shape, kernel, stride, pads, out_hw_):
+        raise ValueError(f"{name}: unsupported geometry: input {tuple(x_shape)}, window {tuple(kernel)}, stride "
+                         f"{tuple(stride)}, top / left pads {tuple(pads)}, output {tuple(out_hw_)}")
+
+
+def pool2d_max_fwd(x, kernel, stride, pads, out_hw_, out=None, idx=None):
+    """(y, idx) of a max pool (csrc/kernels/pool2d.hip).  x [N, H, W, C] bf16; ``kernel`` = (KH,
+    KW), ``stride`` = (sh, sw), ``pads`` = (top, left) -- taps outside the image are skipped --
+    and ``out_hw_`` = (OH, OW).  idx [N, OH, OW, C] uint8 holds the first row-major in-image tap
+    ``kh * KW + kw`` that attains the maximum."""
+    ext = _ext.load(required=True)
+    N, H, W, C = x.shape
+    OH, OW = out_hw_
+    y = out if out is not None else torch.empty((N, OH, OW, C), dtype=torch.bfloat16, device=x.device)
+    _pool_check("pool2d_max_fwd", (x, y), x.shape, kernel, stride, pads, out_hw_)
+    if idx is None:
+        idx = torch.empty((N, OH, OW, C), dtype=torch.uint8, device=x.device)
+    if (tuple(y.shape) != (N, OH, OW, C) or idx.dtype != torch.uint8 or idx.shape != y.shape
+            or not idx.is_contiguous() or not idx.is_cuda):
+        raise ValueError("pool2d_max_fwd: y [N, OH, OW, C] bf16 and a contiguous uint8 idx of its shape expected")
+    ext.pool2d_max_fwd(x.data_ptr(), y.data_ptr(), idx.data_ptr(), N, H, W, C, kernel[0], kernel[1], stride[0],
+                       stride[1], pads[0], pads[1], OH, OW, _st(x.device))
+    if _SHAPE_LOG is not None:
+        _log("poolmax%dx%d" % tuple(kernel), N * OH * OW, C, kernel[0] * kernel[1], _nb(x, y, idx))
+    return y, idx
+
+
+def pool2d_max_bwd(dy, idx, x_shape, kernel, stride, pads, out=None):
+    """dx [N, H, W, C] bf16 of :func:`pool2d_max_fwd` from dy and idx [N, OH, OW, C] (gather form:
+    every dx element is written once; pixels that no window reads get exactly 0)."""
+    ext = _ext.load(required=True)
+    N, H, W, C = x_shape
+    dx = out if out is not None else torch.empty((N, H, W, C), dtype=torch.bfloat16, device=dy.device)
+    _pool_check("pool2d_max_bwd", (dy, dx), x_shape, kernel, stride, pads, tuple(dy.shape[1:3]))
+    if (dy.shape[0] != N or dy.shape[3] != C or tuple(dx.shape) != (N, H, W, C) or idx.dtype != torch.uint8
+            or idx.shape != dy.shape or not idx.is_contiguous() or not idx.is_cuda):
+        raise ValueError("pool2d_max_bwd: dy [N, OH, OW, C] bf16, a contiguous uint8 idx of its shape and dx "
+                         "[N, H, W, C] expected")
+    ext.pool2d_max_bwd(dy.data_ptr(), idx.data_ptr(), dx.data_ptr(), N, H, W, C, kernel[0], kernel[1], stride[0],
+                       stride[1], pads[0], pads[1], dy.shape[1], dy.shape[2], _st(dy.device))
+    if _SHAPE_LOG is not None:
+        _log("poolmaxbwd%dx%d" % tuple(kernel), N * H * W, C, kernel[0] * kernel[1], _nb(dy, idx, dx))
+    return dx
+
+
+def pool2d_avg_fwd(x, kernel, stride, pads, out_hw_, out=None):
+    """y [N, OH, OW, C] bf16 of an average pool whose divisor is the number of in-image taps
+    (TF's ``AveragePooling2D``; arguments as :func:`pool2d_max_fwd`)."""
+    ext = _ext.load(required=True)
+    N, H, W, C = x.shape
+    OH, OW = out_hw_
+    y = out if out is not None else torch.empty((N, OH, OW, C), dtype=torch.bfloat16, device=x.device)
+    _pool_check("pool2d_avg_fwd", (x, y), x.shape, kernel, stride, pads, out_hw_)
+    if tuple(y.shape) != (N, OH, OW, C):
+        raise ValueError("pool2d_avg_fwd: y [N, OH, OW, C] expected")
+    ext.pool2d_avg_fwd(x.data_ptr(), y.data_ptr(), N, H, W, C, kernel[0], kernel[1], stride[0], stride[1], pads[0],
+                       pads[1], OH, OW, _st(x.device))
+    if _SHAPE_LOG is not None:
+        _log("poolavg%dx%d" % tuple(kernel), N * OH * OW, C, kernel[0] * kernel[1], _nb(x, y))
+    return y
+
+
+def pool2d_avg_bwd(dy, x_shape, kernel, stride, pads, out=None):
+    """dx [N, H, W, C] bf16 of :func:`pool2d_avg_fwd` from dy [N, OH, OW, C]: the divisors are
+    recomputed from the geometry; pixels that no window reads get exactly 0."""
+    ext = _ext.load(required=True)
+    N, H, W, C = x_shape
+    dx = out if out is not None else torch.empty((N, H, W, C), dtype=torch.bfloat16, device=dy.device)
+    _pool_check("pool2d_avg_bwd", (dy, dx), x_shape, kernel, stride, pads, tuple(dy.shape[1:3]))
+    if dy.shape[0] != N or dy.shape[3] != C or tuple(dx.shape) != (N, H, W, C):
+        raise ValueError("pool2d_avg_bwd: dy [N, OH, OW, C] and dx [N, H, W, C] expected")
+    ext.pool2d_avg_bwd(dy.data_ptr(), dx.data_ptr(), N, H, W, C, kernel[0], kernel[1], stride[0], stride[1], pads[0],
+                       pads[1], dy.shape[1], dy.shape[2], _st(dy.device))
+    if _SHAPE_LOG is not None:
+        _log("poolavgbwd%dx%d" % tuple(kernel), N * H * W, C, kernel[0] * kernel[1], _nb(dy, dx))
+    return dx
+
+
 # ------------------------------------------- BN folded into the consuming 1x1 GEMM
 XA_BN_RELU, XA_BN_RES_RELU, XA_BN_BWD, XA_BN_RESBN_RELU = 0, 1, 2, 3
 

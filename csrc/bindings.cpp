@@ -148,6 +148,12 @@ int ca_dwconv_dgrad(const bf16_t*, const bf16_t*, bf16_t*, int, int, int, int, i
 long ca_dwconv_wgrad_chunks(int, int, int);
 int ca_dwconv_wgrad(const bf16_t*, const bf16_t*, float*, int, float*, int, int, int, int, int, int, int, int, int,
                     int, int, int, int, hipStream_t);
+int ca_pool2d_max_fwd(const bf16_t*, bf16_t*, uint8_t*, int, int, int, int, int, int, int, int, int, int, int, int,
+                      hipStream_t);
+int ca_pool2d_max_bwd(const bf16_t*, const uint8_t*, bf16_t*, int, int, int, int, int, int, int, int, int, int, int,
+                      int, hipStream_t);
+int ca_pool2d_avg_fwd(const bf16_t*, bf16_t*, int, int, int, int, int, int, int, int, int, int, int, int, hipStream_t);
+int ca_pool2d_avg_bwd(const bf16_t*, bf16_t*, int, int, int, int, int, int, int, int, int, int, int, int, hipStream_t);
 }
 
 #define P(T, x) reinterpret_cast<T>(static_cast<uintptr_t>(x))
@@ -597,5 +603,26 @@ PYBIND11_MODULE(_C, m) {
                            int KH, int KW, int sh, int sw, int pt, int pl, int OH, int OW, u64 s) {
     check(ca_dwconv_wgrad(P(const bf16_t*, dy), P(const bf16_t*, x), P(float*, dw), accumulate, P(float*, ws), Nb, H,
                           W, Cin, DM, KH, KW, sh, sw, pt, pl, OH, OW, S(s)), "dwconv_wgrad");
+  });
+  // max / average pooling at any window (pool2d.hip): top / left pads, OH / OW given
+  m.def("pool2d_max_fwd", [](u64 x, u64 y, u64 idx, int Nb, int H, int W, int C, int KH, int KW, int sh, int sw, int pt,
+                             int pl, int OH, int OW, u64 s) {
+    check(ca_pool2d_max_fwd(P(const bf16_t*, x), P(bf16_t*, y), P(uint8_t*, idx), Nb, H, W, C, KH, KW, sh, sw, pt, pl,
+                            OH, OW, S(s)), "pool2d_max_fwd");
+  });
+  m.def("pool2d_max_bwd", [](u64 dy, u64 idx, u64 dx, int Nb, int H, int W, int C, int KH, int KW, int sh, int sw,
+                             int pt, int pl, int OH, int OW, u64 s) {
+    check(ca_pool2d_max_bwd(P(const bf16_t*, dy), P(const uint8_t*, idx), P(bf16_t*, dx), Nb, H, W, C, KH, KW, sh, sw,
+                            pt, pl, OH, OW, S(s)), "pool2d_max_bwd");
+  });
+  m.def("pool2d_avg_fwd", [](u64 x, u64 y, int Nb, int H, int W, int C, int KH, int KW, int sh, int sw, int pt, int pl,
+                             int OH, int OW, u64 s) {
+    check(ca_pool2d_avg_fwd(P(const bf16_t*, x), P(bf16_t*, y), Nb, H, W, C, KH, KW, sh, sw, pt, pl, OH, OW, S(s)),
+          "pool2d_avg_fwd");
+  });
+  m.def("pool2d_avg_bwd", [](u64 dy, u64 dx, int Nb, int H, int W, int C, int KH, int KW, int sh, int sw, int pt,
+                             int pl, int OH, int OW, u64 s) {
+    check(ca_pool2d_avg_bwd(P(const bf16_t*, dy), P(bf16_t*, dx), Nb, H, W, C, KH, KW, sh, sw, pt, pl, OH, OW, S(s)),
+          "pool2d_avg_bwd");
   });
 }
